@@ -112,7 +112,12 @@ def main():
                     help="N > 1: seconds the rendezvous + RCCL communicator creation may take before the rank exits 124")
     ap.add_argument("--run-timeout", type=float, default=1200.0,
                     help="N > 1: seconds everything after the bootstrap may take before the rank exits 124 (0 = no limit)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the CG solution alpha [1,M] "
+                         "and its 0.5 r.z [1,1]) as DIR/<name>.npy, for output-by-output comparison of two builds")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # Only the JSON line may reach stdout (RCCL prints a version banner there): park fd 1 on stderr
     sys.stdout.flush()
@@ -191,19 +196,25 @@ def main():
 
     def run_steps(k):
         # error_threshold 0 is never met, so exactly k iterations run (device gating keeps count)
-        _, (steps, _) = conjugate_gradient(op, rhs_rows, None, 0.0, max_iterations=k, max_steps_cycle=k + 1,
-                                           check_every=k)
+        sol, (steps, err) = conjugate_gradient(op, rhs_rows, None, 0.0, max_iterations=k, max_steps_cycle=k + 1,
+                                               check_every=k)
         assert int(steps) == k, (int(steps), k)
+        return sol, err
 
     if args.warmup > 0:
         run_steps(args.warmup)
     torch.cuda.synchronize()
     barrier()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    timed_sol, timed_err = run_steps(args.steps)
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the solution is replicated on every rank (the right-hand side and every step's product are all-reduced)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in (("alpha", timed_sol), ("half_rz", timed_err)):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), t.detach().cpu().numpy())
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if args.backend != "nccl":

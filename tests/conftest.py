@@ -9,6 +9,13 @@ for p in (ROOT, PKG):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+# MGP_TESTS_CPU_ONLY=1 (the ASan child of tests/test_sanitizers.py): the process must never initialise the GPU
+# runtime, also on a machine that has a GPU, so torch reports none and every GPU-or-host choice takes the host
+if os.environ.get("MGP_TESTS_CPU_ONLY") == "1":
+    import torch
+
+    torch.cuda.is_available = lambda: False
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")

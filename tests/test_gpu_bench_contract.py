@@ -86,3 +86,27 @@ def test_bench_rank_share_emulation():
     clk = r["sustained_clock"]
     assert 1000 < clk["min_mhz"] <= clk["mean_mhz"] <= clk["max_mhz"] <= 2500 and clk["workgroups_sampled"] >= 8
     assert r["traffic"] is None  # the PMC passes ran at the full size only
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_solve(tmp_path):
+    """`--dump-outputs DIR`: what the last timed step returned (alpha [1,M], 0.5 r.z [1,1]) in float64, the same for
+    two runs with the same arguments (seeded inputs)."""
+    import numpy as np
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                              "--warmup", "1", "--rows", "65536", "--no-extra-legs", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d_line = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+        assert d_line["steps"] == 3 and d_line["roofline"]["launches_timed"] == 6 and d_line["ms_per_step"] > 0
+        return {n: np.load(os.path.join(d, n + ".npy")) for n in ("alpha", "half_rz")}
+
+    a, b = run(tmp_path / "a"), run(tmp_path / "b")
+    assert sorted(os.listdir(tmp_path / "a")) == ["alpha.npy", "half_rz.npy"]
+    assert a["alpha"].shape == (1, 4096) and a["half_rz"].shape == (1, 1)
+    for n in a:
+        assert a[n].dtype == np.float64 and np.all(np.isfinite(a[n]))
+        np.testing.assert_allclose(a[n], b[n], rtol=1e-12, atol=0)
+    assert np.any(a["alpha"] != 0) and a["half_rz"][0, 0] > 0

@@ -44,6 +44,9 @@ def test_host_side_is_clean_under_asan_and_ubsan():
         "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1",
         "MGP_LIBRARY": LIB,            # cggp._hip.lib_path()
         "MGP_HOSTMATH_LIBRARY": LIB,   # tests/test_host_math.py
+        # no GPU runtime under ASan, also on a machine that has a GPU (conftest.py): every test of the child stays
+        # on the host
+        "MGP_TESTS_CPU_ONLY": "1",
     })
     cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider",
            os.path.join(ROOT, "tests", "test_covertree.py"), os.path.join(ROOT, "tests", "test_host_math.py"),
