@@ -121,6 +121,9 @@ SIGNATURES = {
     "mgp_k_dense_vjp": (_I, [_P, _KP, _P, _L, _P, _L, _P, _L, ctypes.POINTER(_D), ctypes.POINTER(_D)]),
     "mgp_segment_sums": (_I, [_P, _I, _P, _P, _P, _L, _L, _L, _P]),
     "mgp_kmm_lambda_matvec": (_I, [_P, _KP, _P, _L, _P, _P, _L, _P]),
+    # random Fourier features (cggp/rff.py)
+    "mgp_rff_features": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, _L]),
+    "mgp_rff_sample": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, ctypes.c_int32, _D, _P, _I]),
     "mgp_profile_enable": (_I, [_P, _I]),
     "mgp_profile_read": (_I, [_P, ctypes.POINTER(_L), ctypes.POINTER(_D)]),
     "mgp_profile_read_each": (_I, [_P, ctypes.POINTER(_D), _L, ctypes.POINTER(_L)]),

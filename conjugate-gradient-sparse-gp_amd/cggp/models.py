@@ -358,6 +358,96 @@ class CGGP(ClusterGP):
                                 seed=self.probe_seed)
 
 
+EPSILON_CONVENTIONS = ("reference", "matheron")
+
+
+def pathwise_epsilon(lambda_diag, num_samples, convention="reference", seed=None, xi=None):
+    """[S, M] noise of the pathwise update from standard normals xi [S, M] (drawn from `seed` when not given).
+
+    "reference": lambda * xi, what `tfd.MultivariateNormalDiag(scale_diag=lambda_diag)` draws in the reference
+    (`cggp/models.py:404-408`), i.e. covariance Lambda^2.  "matheron": sqrt(lambda) * xi, covariance Lambda, the
+    noise Matheron's rule needs for the samples to have `predict_f`'s variance."""
+    lam = torch.as_tensor(lambda_diag).reshape(-1)
+    if xi is None:
+        xi = torch.from_numpy(np.random.default_rng(seed).standard_normal((int(num_samples), lam.shape[0])))
+    xi = torch.as_tensor(xi).to(device=lam.device, dtype=lam.dtype)
+    if convention == "reference":
+        return lam[None, :] * xi
+    if convention == "matheron":
+        return torch.sqrt(lam)[None, :] * xi
+    raise ValueError(f"epsilon must be one of {EPSILON_CONVENTIONS}, got {convention!r}")
+
+
+class PathwiseClusterGP(ClusterGP):
+    """`cggp/models.py:357-420`: the ELBO's likelihood term from pathwise posterior function samples.
+
+    A sample at X is f(X) + K_xz (K_zz + Lambda)^-1 (u - f(Z) - eps), with f one random-Fourier-feature prior draw
+    evaluated at X and Z together (one theta and one W, as the reference concatenates them, :397-402).  Nothing of
+    size N x M or N x L is formed: the prior comes from `mgp_rff_sample` (one fused sweep for D <= 32, S <= 8), the
+    correction K_xz . weights from the multi-column K_nm sweep (`ops.knm_matvec`, R = S).  The [M, M] solve is a
+    Cholesky factorisation, as in the `ClusterGP` twin, or -- with `conjugate_gradient=` -- that CG on K_zz + Lambda
+    with S columns.
+
+    `epsilon="reference"` (default, drop-in) draws eps with scale_diag = lambda, i.e. covariance Lambda^2, as the
+    reference does; `epsilon="matheron"` draws covariance Lambda, for which the sample variance is `predict_f`'s.
+
+    Random draws: numpy PCG64 from `seed` -- theta, then W, then the [S, M] normals of eps.  The values are not
+    differentiable: like the reference, which only evaluates this model, `elbo` returns a float and no gradient
+    flows through the random-feature term."""
+
+    def __init__(self, kernel, likelihood, inducing_variable, *, conjugate_gradient=None, epsilon="reference",
+                 **kwargs):
+        super().__init__(kernel, likelihood, inducing_variable, **kwargs)
+        if epsilon not in EPSILON_CONVENTIONS:
+            raise ValueError(f"epsilon must be one of {EPSILON_CONVENTIONS}, got {epsilon!r}")
+        self.conjugate_gradient = conjugate_gradient
+        self.epsilon = epsilon
+
+    def elbo(self, data, *, num_bases=1, num_samples=1, seed=None):  # :358-371
+        kl = self.prior_kl()
+        likelihood = self.compute_likelihood_term(data, num_bases, num_samples, seed=seed)
+        x, _ = data
+        return likelihood * self.scale(x.shape[0]) - kl
+
+    def compute_likelihood_term(self, data, num_bases, num_samples, *, seed=None):  # :373-388
+        x, y = data
+        num_data = y.shape[0]
+        samples = self.pathwise_samples(x, num_bases, num_samples, seed=seed)  # [S, N, 1]
+        noise = self.likelihood.variance
+        error_squared = (y[None, ...] - samples) ** 2
+        likelihood = error_squared.sum().item() / noise / num_samples
+        constant_term = num_data * math.log(2.0 * math.pi * noise)
+        return -0.5 * (likelihood + constant_term)
+
+    def pathwise_samples(self, sample_at, num_bases, num_samples, *, seed=None, theta=None, weights=None, xi=None):
+        """[S, N, 1] posterior function samples at `sample_at` (:390-420).  `theta` [L, D], `weights` [S, 2L] and
+        `xi` [S, M] (standard normals of eps) may be injected; whatever is not is drawn from `seed`."""
+        from . import rff
+
+        iv, kernel = self.inducing_variable, self.kernel
+        Z = iv.Z
+        n, D = sample_at.shape
+        lambda_diag = self.diag_variance[:, 0]
+        rng = np.random.default_rng(seed)
+        if theta is None:
+            theta = rff.basis_theta_parameter(kernel, num_bases, rng, dim=D)
+        if weights is None:
+            weights = rff.rff_weights(num_samples, num_bases, rng)
+        prior_at = torch.cat([sample_at, Z], dim=0)  # :397
+        prior = rff.rff_sample(prior_at, kernel, num_bases, num_samples, theta=theta, weights=weights)  # [S, N + M]
+        prior_fx, prior_fz = prior[:, :n], prior[:, n:]
+        epsilon = pathwise_epsilon(lambda_diag, num_samples, self.epsilon, rng, xi)  # :404-408
+        solve_against = self.pseudo_u[:, 0][None, :] - prior_fz - epsilon  # [S, M], :414
+        kzz_lambda = Kuu(iv, kernel, jitter=0.0, diag_add=lambda_diag)  # :411-412
+        if self.conjugate_gradient is None:
+            L = torch.linalg.cholesky(kzz_lambda)  # :415-416
+            w = torch.cholesky_solve(solve_against.t().contiguous(), L)  # [M, S]
+        else:
+            w = self.conjugate_gradient(kzz_lambda, solve_against.t().contiguous())
+        correction = ops.knm_matvec(kernel.spec(D), sample_at, Z, w.contiguous(), ops.COLS, ops.ROWS)  # [S, N], :418
+        return (prior_fx + correction)[..., None]  # :419
+
+
 class SGPR:
     """SGPR predictions and bound with the N-sized products done matrix-free (row S1).
 

@@ -274,3 +274,42 @@ def cluster_stats(idx, y, M, method="auto"):
     else:
         raise ValueError(f"unknown method {method!r}")
     return (sums if multi else sums[:, 0].contiguous()), counts
+
+
+def rff_features(X, theta):
+    """Phi [N, 2L] = [cos(X theta^T) | sin(X theta^T)] (`basis_vectors`, reference `cggp/rff.py:48-57`); theta [L, D]
+    in radians."""
+    X = _points(X, "X")
+    theta = _points(theta, "theta", X.shape[1], X.dtype)
+    N, D = X.shape
+    L = theta.shape[0]
+    out = torch.empty((N, 2 * L), dtype=X.dtype, device=X.device)
+    if N == 0 or L == 0:
+        return out
+    hd = _hip.get_handle(X.device)
+    hd.check(hd.lib.mgp_rff_features(hd.h, _hip.dtype_code(X), _hip.ptr(X), N, D, _hip.ptr(theta), L, _hip.ptr(out),
+                                     2 * L))
+    return out
+
+
+def rff_sample(X, theta, W, scale, out_layout=ROWS):
+    """scale * W [S, 2L] @ Phi(X)^T without forming Phi where D <= 32 and S <= 8 (`rff_sample`, reference
+    `cggp/rff.py:60-73`).  out [S, N] (ROWS) or [N, S] (COLS)."""
+    X = _points(X, "X")
+    theta = _points(theta, "theta", X.shape[1], X.dtype)
+    N, D = X.shape
+    L = theta.shape[0]
+    W = _hip.check_tensor(W, "W", dtype=X.dtype)
+    if W.dim() != 2 or W.shape[1] != 2 * L:
+        raise ValueError(f"W must be [S, 2L={2 * L}], got {tuple(W.shape)}")
+    S = W.shape[0]
+    if out_layout not in (COLS, ROWS):
+        raise ValueError(f"bad out_layout {out_layout}")
+    out = torch.empty((S, N) if out_layout == ROWS else (N, S), dtype=X.dtype, device=X.device)
+    if N == 0 or S == 0:
+        return out
+    # L == 0 goes through the C-ABI too: libmgp writes the zeros
+    hd = _hip.get_handle(X.device)
+    hd.check(hd.lib.mgp_rff_sample(hd.h, _hip.dtype_code(X), _hip.ptr(X), N, D, _hip.ptr(theta), L, _hip.ptr(W), S,
+                                   float(scale), _hip.ptr(out), out_layout))
+    return out

@@ -262,6 +262,21 @@ int mgp_segment_sums(mgp_handle* h, int dtype, const int64_t* order, const int64
 int mgp_k_dense_vjp(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B,
                     int64_t nb, const void* G, int64_t ldg, double* dvariance, double* dlengthscales);
 
+/* ---- random Fourier features (the reference's cggp/rff.py; csrc/rff.hip) -------------------------
+ * theta [L, D] spectral frequencies in radians (the library forms theta / 2 pi itself), X [N, D], any D <= MGP_MAX_D.
+ * Phases are reduced in revolutions, so |theta x| of 1e6 rad and more keeps the accuracy of the dot product: per
+ * feature |err| <= 8 u (1 + sum_d |x_d theta_d|), u the unit roundoff of the dtype.
+ * mgp_rff_features: out[n, 0:L] = cos(theta x_n), out[n, L:2L] = sin(theta x_n), rows ld >= 2L apart
+ *   (basis_vectors, rff.py:48-57).
+ * mgp_rff_sample: out(s, n) = scale * sum_l (W[s, l] cos(theta_l x_n) + W[s, L + l] sin(theta_l x_n)), W [S, 2L]
+ *   (cos block first); out [S, N] (MGP_ROWS) or [N, S] (MGP_COLS) (rff_sample, rff.py:60-73).  D <= 32 and S <= 8: one
+ *   fused sweep, deterministic; otherwise feature panels in row chunks of <= ~256 MB and a GEMM against W.
+ * N = 0 writes nothing; L = 0 writes zeros (mgp_rff_sample). */
+int mgp_rff_features(mgp_handle* h, int dtype, const void* X, int64_t N, int32_t D, const void* theta, int64_t L,
+                     void* out, int64_t ld);
+int mgp_rff_sample(mgp_handle* h, int dtype, const void* X, int64_t N, int32_t D, const void* theta, int64_t L,
+                   const void* W, int32_t S, double scale, void* out, int out_layout);
+
 /* ---- measurement (bench.py): HIP events around every launch of the fused sweep kernel ------
  * While enabled, each sweep launch is bracketed by two events on the handle's stream;
  * mgp_profile_read synchronises the stream, returns the number of bracketed launches and the
