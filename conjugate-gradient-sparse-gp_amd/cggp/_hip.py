@@ -19,7 +19,7 @@ F32, F64 = 0, 1
 SE, MATERN12, MATERN32, MATERN52 = 0, 1, 2, 3
 COLS, ROWS = 0, 1
 PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK = 0, 1, 2, 3, 4
-OP_DENSE, OP_SGPR, OP_KMM_LAMBDA = 0, 1, 2
+OP_DENSE, OP_SGPR, OP_KMM_LAMBDA, OP_KXX_NOISE = 0, 1, 2, 3
 
 KERNEL_KINDS = {"se": SE, "matern12": MATERN12, "matern32": MATERN32, "matern52": MATERN52}
 
@@ -121,6 +121,7 @@ SIGNATURES = {
     "mgp_k_dense_vjp": (_I, [_P, _KP, _P, _L, _P, _L, _P, _L, ctypes.POINTER(_D), ctypes.POINTER(_D)]),
     "mgp_segment_sums": (_I, [_P, _I, _P, _P, _P, _L, _L, _L, _P]),
     "mgp_kmm_lambda_matvec": (_I, [_P, _KP, _P, _L, _P, _P, _L, _P]),
+    "mgp_kxx_matvec": (_I, [_P, _KP, _P, _L, _D, _P, ctypes.c_int32, _I, _P, _I]),
     # random Fourier features (cggp/rff.py)
     "mgp_rff_features": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, _L]),
     "mgp_rff_sample": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, ctypes.c_int32, _D, _P, _I]),

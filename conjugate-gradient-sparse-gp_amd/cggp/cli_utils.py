@@ -15,7 +15,7 @@ import torch
 from . import kernels as _kernels
 from . import selection
 from .likelihoods import Gaussian
-from .models import CGGP, SGPR, cdgp_class, sgpr_class  # noqa: F401  (re-exported as in the reference)
+from .models import CGGP, GPR, SGPR, cdgp_class, create_gpr_model, gpr_class, sgpr_class  # noqa: F401  (re-exported as in the reference)
 from .optimize import (assign_inducing_parameters, covertree_update_inducing_parameters,
                        kmeans_update_inducing_parameters, oips_update_inducing_parameters)
 

@@ -122,6 +122,41 @@ class KmmLambdaOperator(LinearOperator):
         return self.lam + self.kernel.variance
 
 
+class KxxNoiseOperator(LinearOperator):
+    """(k(X,X) + noise_variance I) applied matrix-free, each unordered pair of rows once (`mgp_kxx_matvec`): the
+    system of exact GP regression, `GPR`'s K + s2 I without the [N,N] matrix.  Single device."""
+
+    def __init__(self, kernel, X, noise_variance):
+        self.X = _hip.check_tensor(X, "X")
+        if self.X.dim() != 2:
+            raise ValueError(f"X must be [N, D], got {tuple(self.X.shape)}")
+        self.noise_variance = float(noise_variance)
+        if not self.noise_variance >= 0.0:
+            raise ValueError("noise_variance must be >= 0")
+        self.kernel = kernel
+        self.spec = kernel.spec(self.X.shape[1])
+        N = self.X.shape[0]
+        self.shape = (N, N)
+        self.dtype = self.X.dtype
+        self.device = self.X.device
+
+    def _struct(self):
+        k = self.spec.struct(_hip.dtype_code(self.X))
+        st = _hip.MgpOperator()
+        st.kind = _hip.OP_KXX_NOISE
+        st.dtype = k.dtype
+        st.n = self.shape[0]
+        st.kernel = ctypes.pointer(k)
+        st.X = self.X.data_ptr()
+        st.N = self.shape[0]
+        st.s2 = self.noise_variance
+        return st, (k, self.X)
+
+    def diag(self):
+        return torch.full((self.shape[0],), self.kernel.variance + self.noise_variance, dtype=self.dtype,
+                          device=self.device)
+
+
 class SgprNormalOperator(LinearOperator):
     """S = s2 (Kmm + jitter I) + K_mn K_nm over this rank's rows of X (row S1).
 

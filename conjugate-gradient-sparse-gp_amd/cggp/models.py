@@ -3,6 +3,7 @@
 `CGGP` (the CDGP model: every (Kmm+Lambda)^-1 applied by CG), its Cholesky twin `ClusterGP`,
 `eval_logdet`, and a CG form of SGPR.  Names, constructor keywords, method signatures and
 returned shapes follow the reference (`cggp/models.py:21-48,176-354`, `cggp/cli_utils.py:439-446`);
+`GPR` is the exact regression baseline the reference takes from GPflow (`gpr_class`, `cggp/cli_utils.py:449-452`);
 kernel evaluation, the K_nm products, the dense `p @ A` and the CG loop run in libmgp.
 """
 
@@ -12,7 +13,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .conjugate_gradient import ConjugateGradient, SgprNormalOperator, SubsampledNormalPreconditioner
+from .conjugate_gradient import ConjugateGradient, KxxNoiseOperator, SgprNormalOperator, SubsampledNormalPreconditioner
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
 
@@ -644,6 +645,170 @@ class SGPR:
         quad = -0.5 * yy / s2 + 0.5 * (c * c).sum().item()
         trace = -0.5 * N * kernel.variance / s2 + 0.5 * AAT.diagonal().sum().item()
         return const + logdet + quad + trace
+
+
+class GPR:
+    """Exact GP regression: GPflow `GPR`'s surface (`gpflow.models.GPR(data, kernel, noise_variance)`), the baseline the
+    reference builds through `gpr_class` / `create_gpr_model` (`cggp/cli_utils.py:171-184,449-452`) and whose
+    `predict_f(x, full_cov=True)` is the ground truth of `paper_condition_wasserstein.py:60-135`.
+
+    Two ways to solve with K + s2 I:
+      "cholesky": `mgp_k_dense` forms it, `torch.linalg.cholesky` factors it -- GPflow's own arithmetic;
+      "cg":       `KxxNoiseOperator`, matrix-free, through the model's `conjugate_gradient`:
+                  alpha = (K + s2 I)^-1 y, mean = k(X*, X) alpha, and the variance solves (K + s2 I) W = K_X*
+                  for the test columns in chunks of at most `variance_chunk_bytes` of K_X*.
+      "auto":     Cholesky up to `cholesky_max_n` rows, CG above.
+    `log_marginal_likelihood` needs log|K + s2 I| and exists on the Cholesky path only.
+    """
+
+    def __init__(self, data, kernel, noise_variance=1.0, conjugate_gradient=None, *, solver="auto",
+                 cholesky_max_n=16384, variance_chunk_bytes=256 << 20):
+        if solver not in ("auto", "cholesky", "cg"):
+            raise ValueError(f"unknown solver {solver!r}")
+        X, Y = data
+        if X.dim() != 2 or Y.dim() != 2 or Y.shape[0] != X.shape[0]:
+            raise ValueError(f"data must be (X [N, D], Y [N, P]), got {tuple(X.shape)}, {tuple(Y.shape)}")
+        self.data = (X, Y)
+        self.kernel = kernel
+        self.likelihood = Gaussian(noise_variance)
+        self.conjugate_gradient = conjugate_gradient or ConjugateGradient(1e-6)
+        self.solver = solver
+        self.cholesky_max_n = int(cholesky_max_n)
+        self.variance_chunk_bytes = int(variance_chunk_bytes)
+        self.invalidate()
+
+    # ---- caches (alpha, the factor, the operator): functions of X, Y, the kernel and the noise, which
+    # `multiple_assign` and the training loop change from outside -- dropped when the fingerprint moves (as SGPR)
+    def invalidate(self):
+        self._L = None
+        self._alpha = None
+        self._op = None
+        self._key = self._fingerprint()
+        self._key_refs = self.data
+
+    def _fingerprint(self):
+        X, Y = self.data
+        k = self.kernel
+        return (id(X), X._version, tuple(X.shape), id(Y), Y._version, tuple(Y.shape), type(k).__name__,
+                float(k.variance), tuple(float(v) for v in k.lengthscales), float(self.likelihood.variance),
+                id(self.conjugate_gradient), self.solver, self.cholesky_max_n)
+
+    def _sync(self):
+        if self._fingerprint() != self._key:
+            self.invalidate()
+
+    def uses_cholesky(self):
+        return self.solver == "cholesky" or (self.solver == "auto" and self.data[0].shape[0] <= self.cholesky_max_n)
+
+    def _spec(self):
+        return self.kernel.spec(self.data[0].shape[1])
+
+    def cholesky(self):
+        """L = chol(K + s2 I) (GPflow GPR: add_likelihood_noise_cov, then cholesky); formed once, cached."""
+        self._sync()
+        if self._L is None:
+            X = self.data[0]
+            self._L = torch.linalg.cholesky(ops.k_dense(self._spec(), X, X, jitter=self.likelihood.variance))
+        return self._L
+
+    def operator(self):
+        """K + s2 I as a matrix-free operator (`KxxNoiseOperator`)."""
+        self._sync()
+        if self._op is None:
+            self._op = KxxNoiseOperator(self.kernel, self.data[0], self.likelihood.variance)
+        return self._op
+
+    def solve(self, rhs):
+        """(K + s2 I)^-1 rhs for rhs [N, R]."""
+        self._sync()
+        if self.uses_cholesky():
+            return torch.cholesky_solve(rhs, self.cholesky())
+        return self.conjugate_gradient(self.operator(), rhs.contiguous())
+
+    def alpha(self):
+        self._sync()
+        if self._alpha is None:
+            self._alpha = self.solve(self.data[1])
+        return self._alpha
+
+    def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
+        """mean [B, P]; variance [B, P] or covariance [P, B, B] (GPflow GPR.predict_f, P = 1 output here)."""
+        assert not full_output_cov
+        self._sync()
+        X, Y = self.data
+        spec = self._spec()
+        P = Y.shape[1]
+        if self.uses_cholesky():
+            L = self.cholesky()
+            Kmn = ops.k_dense(spec, X, Xnew)  # [N, B]
+            A = torch.linalg.solve_triangular(L, Kmn, upper=False)
+            v = torch.linalg.solve_triangular(L, Y, upper=False)
+            mean = A.t() @ v
+            if full_cov:
+                cov = ops.k_dense(spec, Xnew, Xnew) - A.t() @ A
+                return mean, cov[None, ...].expand(P, -1, -1).contiguous()
+            var = self.kernel.K_diag(Xnew) - (A * A).sum(dim=0)
+            return mean, var[:, None].expand(-1, P).contiguous()
+        mean = ops.knm_matvec(spec, Xnew, X, self.alpha())
+        B, N = Xnew.shape[0], X.shape[0]
+        step = max(1, min(B, self.variance_chunk_bytes // max(1, N * X.element_size())))
+        if full_cov:
+            cov = ops.k_dense(spec, Xnew, Xnew)
+        else:
+            var = self.kernel.K_diag(Xnew).clone()
+        for c0 in range(0, B, step):
+            xs = Xnew[c0:c0 + step]
+            Kc = ops.k_dense(spec, X, xs)  # [N, bc]
+            Wc = self.conjugate_gradient(self.operator(), Kc)
+            if full_cov:
+                cov[:, c0:c0 + step] -= ops.knm_matvec(spec, Xnew, X, Wc)  # K_*X W = K_*X (K + s2 I)^-1 K_X*
+            else:
+                var[c0:c0 + step] -= ops.colwise_dot(Kc, Wc)
+        if full_cov:
+            cov = 0.5 * (cov + cov.t())
+            return mean, cov[None, ...].expand(P, -1, -1).contiguous()
+        return mean, var[:, None].expand(-1, P).contiguous()
+
+    def predict_y(self, Xnew, full_cov=False, full_output_cov=False):
+        mean, var = self.predict_f(Xnew, full_cov=full_cov, full_output_cov=full_output_cov)
+        if full_cov:
+            eye = torch.eye(var.shape[-1], dtype=var.dtype, device=var.device)
+            return mean, var + self.likelihood.variance * eye
+        return mean, var + self.likelihood.variance
+
+    def log_marginal_likelihood(self):
+        """log N(y | 0, K + s2 I), GPflow GPR.log_marginal_likelihood (multivariate_normal on the Cholesky factor)."""
+        self._sync()
+        if not self.uses_cholesky():
+            raise NotImplementedError(
+                "GPR.log_marginal_likelihood needs log|K + s2 I|, which the CG path does not form (a stochastic "
+                "Lanczos estimate is not implemented); use solver='cholesky' or raise cholesky_max_n")
+        X, Y = self.data
+        L = self.cholesky()
+        v = torch.linalg.solve_triangular(L, Y, upper=False)
+        N, P = Y.shape
+        logdet = torch.log(L.diagonal()).sum().item()
+        return -0.5 * N * P * math.log(2.0 * math.pi) - P * logdet - 0.5 * (v * v).sum().item()
+
+    def maximum_log_likelihood_objective(self):
+        return self.log_marginal_likelihood()
+
+    def training_loss(self):
+        return -self.maximum_log_likelihood_objective()
+
+
+def gpr_class(train_data, kernel, likelihood, **kwargs):
+    """`cggp/cli_utils.py:449-452` (GPflow GPR there)."""
+    return GPR(train_data, kernel, noise_variance=likelihood.variance, **kwargs)
+
+
+def create_gpr_model(train_data, _kernel_fn, **model_kwargs):
+    """`cggp/cli_utils.py:171-184`: noise variance 0.1 and the module's `kernel_fn(dim)` (the reference, too, ignores
+    its `_kernel_fn` argument)."""
+    from .cli_utils import kernel_fn
+
+    dim = train_data[0].shape[-1]
+    return GPR(train_data, kernel_fn(dim), noise_variance=0.1, **model_kwargs)
 
 
 def cdgp_class(kernel, likelihood, iv, error_threshold=1e-6, **kwargs):

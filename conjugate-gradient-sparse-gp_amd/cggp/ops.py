@@ -61,6 +61,31 @@ def knm_matvec(spec, X, Z, V, v_layout=COLS, out_layout=None):
     return out
 
 
+def kxx_matvec(spec, X, s2, V, v_layout=COLS, out_layout=None):
+    """out = (k(X, X) + s2 I) @ V, each unordered pair of rows evaluated once (fp64, D <= 32).
+    V [N,R] (COLS) or [R,N] (ROWS); out [N,R] or [R,N]."""
+    X = _points(X, "X", spec.D)
+    V = _hip.check_tensor(V, "V", dtype=X.dtype)
+    if V.dim() != 2:
+        raise ValueError("V must be 2-D")
+    N = X.shape[0]
+    R = V.shape[1] if v_layout == COLS else V.shape[0]
+    if (V.shape[0] if v_layout == COLS else V.shape[1]) != N:
+        raise ValueError(f"V shape {tuple(V.shape)} does not match N={N}")
+    s2 = float(s2)
+    if not s2 >= 0.0:
+        raise ValueError("s2 must be >= 0")
+    out_layout = v_layout if out_layout is None else out_layout
+    out = torch.empty((N, R) if out_layout == COLS else (R, N), dtype=X.dtype, device=X.device)
+    if N == 0 or R == 0:
+        return out
+    hd = _hip.get_handle(X.device)
+    k = spec.struct(_hip.dtype_code(X))
+    hd.check(hd.lib.mgp_kxx_matvec(hd.h, ctypes.byref(k), _hip.ptr(X), N, s2, _hip.ptr(V), R, v_layout,
+                                   _hip.ptr(out), out_layout))
+    return out
+
+
 def kmn_matvec(spec, X, Z, W, w_layout=COLS, out_layout=None):
     """out = k(Z, X) @ W = K_nm^T W.  W [N,R] (COLS) or [R,N] (ROWS); out [M,R] or [R,M]."""
     X = _points(X, "X", spec.D)

@@ -206,6 +206,39 @@ class TrainableCGGP:
                     num_data=self.num_data)
 
 
+class TrainableGPR:
+    """Exact GP regression with trainable kernel and noise (the `paper_cli_gpr.py` flow: L-BFGS on the marginal
+    likelihood).  `training_loss` is -log N(y | 0, K + s2 I) with K through `TrainableKernel.K` (`mgp_k_dense` forward,
+    `mgp_k_dense_vjp` backward) and a torch Cholesky; no probes (`num_probes = None`)."""
+
+    def __init__(self, kernel, noise_variance, X, Y):
+        self.kernel = TrainableKernel(kernel)
+        self.likelihood_variance = Parameter(noise_variance)
+        self.X, self.Y = X, Y
+        self.num_probes = None
+
+    def parameters(self):
+        return self.kernel.parameters() + [self.likelihood_variance.raw]
+
+    def log_marginal_likelihood(self, data=None):
+        X, Y = (self.X, self.Y) if data is None else data
+        N, P = Y.shape
+        s2 = self.likelihood_variance()
+        K = self.kernel.K(X) + s2.to(X.device) * torch.eye(N, dtype=X.dtype, device=X.device)
+        L = torch.linalg.cholesky(K)
+        v = torch.linalg.solve_triangular(L, Y, upper=False)
+        return (-0.5 * N * P * math.log(2.0 * math.pi) - P * torch.log(L.diagonal()).sum()
+                - 0.5 * (v * v).sum())
+
+    def training_loss(self, data=None, probes=None):
+        return -self.log_marginal_likelihood(data)
+
+    def frozen_model(self):
+        from .models import GPR
+        return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
+                   solver="cholesky")
+
+
 def train_using_adam_and_update(data, model, iterations, batch_size, learning_rate, update_fn=None,
                                 update_during_training=None, monitor=None, seed=0):
     """`cggp/optimize.py:198-254`: shuffled minibatches, one Adam step per iteration, optional

@@ -402,6 +402,8 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
       MGP_LAUNCH_CHECK(h);
       return MGP_OK;
     }
+    case MGP_OP_KXX_NOISE:  // (k(X,X) + s2 I) p, each unordered pair once (kxx.hip); rows of P are the right-hand sides
+      return mgp_kxx(h, op->kernel, op->X, n, op->s2, VecView{P, 1, n}, (int)Bt, VecViewMut{out, 1, n}, gate);
     case MGP_OP_SGPR: {
       // u[Bt,N] = (K_nm p^T)^T ; t[Bt,M] = (K_mn u^T)^T over the local rows ; the replicated
       // s2*Kmm.p term is added as this rank's row slab of it, so ONE all-reduce of t finishes S.p
@@ -518,6 +520,12 @@ int check_operator(mgp_handle* h, const mgp_operator* op) {
       return mgp_fail(h, MGP_E_BADARG, "give either the allreduce hook or a communicator, not both");
     if (op->kind == MGP_OP_SGPR && op->allreduce && op->world_size < 1)
       return mgp_fail(h, MGP_E_BADARG, "allreduce hook needs world_size >= 1");
+  } else if (op->kind == MGP_OP_KXX_NOISE) {
+    MGP_TRY(mgp_check_kernel(h, op->kernel));
+    if (op->kernel->dtype != op->dtype) return mgp_fail(h, MGP_E_DTYPE, "operator/kernel dtype mismatch");
+    if (op->N != op->n || !op->X) return mgp_fail(h, MGP_E_SHAPE, "K_XX operator needs X with N == n");
+    if (!(op->s2 >= 0.0)) return mgp_fail(h, MGP_E_BADARG, "K_XX operator needs s2 >= 0");
+    if (op->allreduce || op->comm) return mgp_fail(h, MGP_E_BADARG, "K_XX operator is single-rank (no allreduce / comm)");
   } else {
     return mgp_fail(h, MGP_E_BADARG, "unknown operator kind %d", op->kind);
   }

@@ -25,6 +25,12 @@ struct mgp_handle {
   // operator scratch (u = K_nm p and the [Bt,M] partial of the SGPR operator)
   void* opws = nullptr;
   size_t opws_bytes = 0;
+  // symmetric self-product scratch (kxx.hip): packed set, weights, running sum, slots of the band launches
+  void* kxx = nullptr;
+  size_t kxx_bytes = 0;
+  int kxx_mode = 0;  // mgp_kxx_matvec / MGP_OP_KXX_NOISE: 0 = symmetric kernel where it serves (fp64, D <= 32, N >=
+                     // kxx_min_n), 1 = wherever it can (MGP_KXX=sym), 2 = the plain sweep mgp_sweep(X, X) + s2 V (MGP_KXX=plain)
+  long kxx_min_n = 1L << 16;  // MGP_KXX_MIN_N
   // generic-D scratch (transposed multipliers, kernel panel, chunk output)
   void* gen = nullptr;
   size_t gen_bytes = 0;
@@ -337,6 +343,9 @@ inline VecViewMut mgp_view_mut(void* p, int64_t n, int64_t R, int layout) {
 // out(i,r) = variance * sum_j k(a_i, b_j) w(j,r) [+ alpha * addend(i,r)];  gate: device int, skip if 0
 int mgp_sweep(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
               VecView W, int32_t R, VecViewMut out, double alpha, VecView addend, const int* gate);
+// kxx.hip: out(i,r) = variance * sum_j k(x_i, x_j) v(j,r) + s2 v(i,r), each unordered pair evaluated once
+int mgp_kxx(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, VecView V, int32_t R,
+            VecViewMut out, const int* gate);
 // generic-D forms (generic.hip): explicit panels + NT GEMM, any D <= MGP_MAX_D
 int mgp_k_dense_generic(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
                         void* out, int64_t ld, double jitter, const void* diag_add, const int* gate);

@@ -54,7 +54,9 @@ enum { MGP_COLS = 0, MGP_ROWS = 1 };
 
 enum { MGP_PRE_EYE = 0, MGP_PRE_JACOBI = 1, MGP_PRE_BLOCK = 2, MGP_PRE_DENSE = 3, MGP_PRE_CALLBACK = 4 };
 
-enum { MGP_OP_DENSE = 0, MGP_OP_SGPR = 1, MGP_OP_KMM_LAMBDA = 2 };
+/* MGP_OP_KXX_NOISE: (k(X,X) + s2 I) applied matrix-free with each unordered pair evaluated once (mgp_kxx_matvec);
+ * fields kernel, X, N, s2 and n == N; single rank: `allreduce` / `comm` set is MGP_E_BADARG */
+enum { MGP_OP_DENSE = 0, MGP_OP_SGPR = 1, MGP_OP_KMM_LAMBDA = 2, MGP_OP_KXX_NOISE = 3 };
 
 typedef struct mgp_handle mgp_handle;
 /* one RCCL communicator rank (wraps ncclComm_t); see "collectives" below */
@@ -184,6 +186,21 @@ int mgp_kmn_knm(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, co
  * preconditioner of the SGPR normal equations (build-side addition, no reference counterpart). */
 int mgp_kmn_sq_colsum(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z,
                       int64_t M, void* out);
+
+/* ---- symmetric self-product: the exact GP regression operator ------------------------------------------------
+ * out[N,R] = (k(X,X) + s2 I) V, matrix-free.  The reference's exact baseline is GPflow's GPR (gpr_class,
+ * cggp/cli_utils.py:449-452; create_gpr_model, cli_utils.py:171-184), which forms this N x N matrix and factors it;
+ * here it is the operator of a CG solve (MGP_OP_KXX_NOISE) for N far beyond a dense K.  Layouts and the empty input
+ * follow mgp_knm_matvec (N = 0 writes nothing).  One right-hand side, fp64, D <= MGP_FUSED_MAX_D, N >= 2^16: each
+ * unordered pair {i, j} is evaluated once and feeds both rows (csrc/kxx.hip), the same expansion-form distance and exp2
+ * arithmetic as the sweep; deterministic (no float atomics, fixed summation order).  Otherwise (several columns, small
+ * N, fp32, D > 32; or MGP_KXX=plain in the environment) the sweep k(X,X) V plus s2 V (mgp_knm_matvec with Z = X),
+ * which measured faster there.  MGP_KXX=sym takes the symmetric kernel wherever it can (fp64, D <= 32).
+ * Scratch, one arena of the handle (counted by mgp_workspace_bytes; MGP_E_NOMEM from a fixed pool that is too small):
+ * at most max(2^29, 128 N') + 8 N' (D' + 17) + 256 bytes, N' = N rounded up to 1024, D' = D rounded up to 4, 8, 16
+ * or 32 -- O(N), nothing N x N (N = 2^20, D = 32, R = 8: 904 MiB). */
+int mgp_kxx_matvec(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, const void* V, int32_t R,
+                   int v_layout, void* out, int out_layout);
 
 /* ---- dense symmetric product (row M2: `state.p @ A`, conjugate_gradient.py:65) ---------
  * out[Bt,n] = P[Bt,n] @ A[n,n] for SYMMETRIC A (CG requires it; computed as rows of A dotted
