@@ -122,6 +122,9 @@ SIGNATURES = {
     "mgp_segment_sums": (_I, [_P, _I, _P, _P, _P, _L, _L, _L, _P]),
     "mgp_kmm_lambda_matvec": (_I, [_P, _KP, _P, _L, _P, _P, _L, _P]),
     "mgp_kxx_matvec": (_I, [_P, _KP, _P, _L, _D, _P, ctypes.c_int32, _I, _P, _I]),
+    "mgp_kxx_grad": (_I, [_P, _KP, _P, _L, _P, _P, ctypes.c_int32, _I, ctypes.POINTER(_D), ctypes.POINTER(_D)]),
+    "mgp_pcg_solve_record": (_I, [_P, ctypes.POINTER(MgpOperator), ctypes.POINTER(MgpPrecond), _P, _P, _L, _D,
+                                  _L, _L, _D, ctypes.c_int32, _P, _P, ctypes.POINTER(MgpCgStats), _P, _L]),
     # random Fourier features (cggp/rff.py)
     "mgp_rff_features": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, _L]),
     "mgp_rff_sample": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, ctypes.c_int32, _D, _P, _I]),

@@ -8,6 +8,7 @@ kernel evaluation, the K_nm products, the dense `p @ A` and the CG loop run in l
 """
 
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -16,6 +17,7 @@ from . import ops
 from .conjugate_gradient import ConjugateGradient, KxxNoiseOperator, SgprNormalOperator, SubsampledNormalPreconditioner
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
+from .slq import slq_log_quadratic
 
 
 def rademacher(shape, dtype, device, seed):
@@ -647,6 +649,12 @@ class SGPR:
         return const + logdet + quad + trace
 
 
+LMLEstimate = namedtuple("LMLEstimate", ["value", "log_det", "data_fit", "std_error", "iterations", "converged"])
+LMLEstimate.__doc__ = """`GPR.log_marginal_likelihood_estimate`: value = -1/2 data_fit - 1/2 P log_det - 1/2 N P log(2 pi),
+data_fit = sum y^T (K + s2 I)^-1 y, std_error = the spread of the per-probe log-det terms / sqrt(t), iterations and
+converged of the one CG solve."""
+
+
 class GPR:
     """Exact GP regression: GPflow `GPR`'s surface (`gpflow.models.GPR(data, kernel, noise_variance)`), the baseline the
     reference builds through `gpr_class` / `create_gpr_model` (`cggp/cli_utils.py:171-184,449-452`) and whose
@@ -658,7 +666,8 @@ class GPR:
                   alpha = (K + s2 I)^-1 y, mean = k(X*, X) alpha, and the variance solves (K + s2 I) W = K_X*
                   for the test columns in chunks of at most `variance_chunk_bytes` of K_X*.
       "auto":     Cholesky up to `cholesky_max_n` rows, CG above.
-    `log_marginal_likelihood` needs log|K + s2 I| and exists on the Cholesky path only.
+    `log_marginal_likelihood` needs log|K + s2 I| and exists on the Cholesky path only;
+    `log_marginal_likelihood_estimate` is its matrix-free stochastic Lanczos estimate at any N.
     """
 
     def __init__(self, data, kernel, noise_variance=1.0, conjugate_gradient=None, *, solver="auto",
@@ -781,14 +790,54 @@ class GPR:
         self._sync()
         if not self.uses_cholesky():
             raise NotImplementedError(
-                "GPR.log_marginal_likelihood needs log|K + s2 I|, which the CG path does not form (a stochastic "
-                "Lanczos estimate is not implemented); use solver='cholesky' or raise cholesky_max_n")
+                "GPR.log_marginal_likelihood needs log|K + s2 I|, which the CG path does not form; use "
+                "log_marginal_likelihood_estimate() (stochastic Lanczos quadrature), solver='cholesky' or raise "
+                "cholesky_max_n")
         X, Y = self.data
         L = self.cholesky()
         v = torch.linalg.solve_triangular(L, Y, upper=False)
         N, P = Y.shape
         logdet = torch.log(L.diagonal()).sum().item()
         return -0.5 * N * P * math.log(2.0 * math.pi) - P * logdet - 0.5 * (v * v).sum().item()
+
+    def log_marginal_likelihood_estimate(self, num_probes=15, seed=0, probes=None):
+        """Matrix-free estimate of log N(y | 0, K + s2 I), whatever `solver` is set (`LMLEstimate`).
+
+        One CG solve on the `KxxNoiseOperator` with the columns [Y, Z] (t Rademacher probes Z [N, t] drawn from a
+        seeded CPU `torch.Generator`, or `probes`), each normalised to unit norm so that the model's `error_threshold`
+        acts per column and relative, records its step lengths and direction ratios (`ops.pcg_solve_record`).
+        alpha = (K + s2 I)^-1 Y gives the data fit; the probe columns' Lanczos tridiagonals give
+        log|K + s2 I| ~= (1/t) sum_i |z_i|^2 e1^T log(T_i) e1 (stochastic Lanczos quadrature, `cggp.slq`)."""
+        return self._lml_estimate(num_probes, seed, probes)[0]
+
+    def _lml_estimate(self, num_probes=15, seed=0, probes=None, conjugate_gradient=None):
+        """(LMLEstimate, alpha [N, P], (K + s2 I)^-1 Z [N, t], Z [N, t])."""
+        self._sync()
+        X, Y = self.data
+        N, P = Y.shape
+        if probes is None:
+            gen = torch.Generator().manual_seed(int(seed))
+            probes = torch.randint(0, 2, (N, int(num_probes)), generator=gen, dtype=torch.int64) * 2 - 1
+        probes = probes.to(device=X.device, dtype=X.dtype)
+        if probes.dim() != 2 or probes.shape[0] != N or probes.shape[1] < 1:
+            raise ValueError(f"probes must be [N={N}, t >= 1], got {tuple(probes.shape)}")
+        t = probes.shape[1]
+        cg = conjugate_gradient or self.conjugate_gradient
+        B = torch.cat([Y, probes], dim=1).t().contiguous()  # [P + t, N]: the solve's rows are the columns
+        norms = torch.linalg.vector_norm(B, dim=1, keepdim=True)
+        scale = torch.where(norms > 0, norms, torch.ones_like(norms))
+        sol, _, stats, coef = ops.pcg_solve_record(
+            self.operator(), B / scale, cg.error_threshold, cg.max_iterations, cg.min_float, cg.check_every)
+        sol = sol * scale
+        alpha, W = sol[:P].t(), sol[P:].t()
+        quads, _ = slq_log_quadratic(coef[:, P:, :].cpu().numpy(), (norms[P:, 0] ** 2).cpu().numpy(),
+                                     cg.error_threshold, cg.min_float)
+        log_det = float(np.mean(quads))
+        std_error = float(np.std(quads, ddof=1) / math.sqrt(t)) if t > 1 else float("nan")
+        data_fit = float((Y * alpha).sum())
+        value = -0.5 * data_fit - 0.5 * P * log_det - 0.5 * N * P * math.log(2.0 * math.pi)
+        est = LMLEstimate(value, log_det, data_fit, std_error, int(stats.iterations), bool(stats.converged))
+        return est, alpha, W, probes
 
     def maximum_log_likelihood_objective(self):
         return self.log_marginal_likelihood()

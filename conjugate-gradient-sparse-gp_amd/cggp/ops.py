@@ -86,6 +86,53 @@ def kxx_matvec(spec, X, s2, V, v_layout=COLS, out_layout=None):
     return out
 
 
+def kxx_grad(spec, X, U, V, layout=COLS):
+    """(sum_r u_r^T dK/dvariance v_r: float, [sum_r u_r^T dK/dl_d v_r for d < D]) for K = k(X, X) without noise, every
+    pair of rows (diagonal included), nothing N x N formed.  U, V [N, R] (COLS) or [R, N] (ROWS)."""
+    X = _points(X, "X", spec.D)
+    U = _hip.check_tensor(U, "U", dtype=X.dtype)
+    V = _hip.check_tensor(V, "V", dtype=X.dtype)
+    N = X.shape[0]
+    if U.dim() != 2 or U.shape != V.shape or (U.shape[0] if layout == COLS else U.shape[1]) != N:
+        raise ValueError(f"U {tuple(U.shape)} and V {tuple(V.shape)} must both be [N={N}, R] (COLS) or [R, N] (ROWS)")
+    R = U.shape[1] if layout == COLS else U.shape[0]
+    dvar = ctypes.c_double(0.0)
+    dls = (ctypes.c_double * _hip.MGP_MAX_D)()
+    if N and R:
+        hd = _hip.get_handle(X.device)
+        k = spec.struct(_hip.dtype_code(X))
+        hd.check(hd.lib.mgp_kxx_grad(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(U), _hip.ptr(V), R, layout,
+                                     ctypes.byref(dvar), dls))
+    return dvar.value, [dls[d] for d in range(spec.D)]
+
+
+def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e-16, check_every=10):
+    """CG from zero on `op` (a `conjugate_gradient.LinearOperator`) for the rows of rhs [Bt, n], identity
+    preconditioner, no residual refresh, recording every step taken (`mgp_pcg_solve_record`).
+
+    Returns (solution [Bt, n], err [Bt, 1] = 0.5 rz, stats, coef [steps, Bt, 3] = (gamma, beta, 0.5 rz after the step))."""
+    rhs = _hip.check_tensor(rhs, "rhs", dtype=op.dtype)
+    if rhs.dim() != 2 or rhs.shape[1] != op.shape[0]:
+        raise ValueError(f"rhs must be [Bt, n={op.shape[0]}], got {tuple(rhs.shape)}")
+    Bt, n = rhs.shape
+    max_iterations = n if max_iterations is None else int(max_iterations)
+    sol = torch.empty_like(rhs)
+    err = torch.empty((Bt, 1), dtype=op.dtype, device=op.device)
+    coef = torch.zeros((max(max_iterations, 0), Bt, 3), dtype=op.dtype, device=op.device)
+    stats = _hip.MgpCgStats()
+    if Bt > 0:
+        hd = _hip.get_handle(op.device)
+        st, keep = op._struct()
+        pre = _hip.MgpPrecond()
+        pre.kind = _hip.PRE_EYE
+        hd.check(hd.lib.mgp_pcg_solve_record(
+            hd.h, ctypes.byref(st), ctypes.byref(pre), _hip.ptr(rhs), None, Bt, float(error_threshold), max_iterations,
+            max_iterations + 1, float(min_float), int(check_every), _hip.ptr(sol), _hip.ptr(err), ctypes.byref(stats),
+            _hip.ptr(coef), coef.shape[0]))
+        del keep
+    return sol, err, stats, coef[:stats.iterations]
+
+
 def kmn_matvec(spec, X, Z, W, w_layout=COLS, out_layout=None):
     """out = k(Z, X) @ W = K_nm^T W.  W [N,R] (COLS) or [R,N] (ROWS); out [M,R] or [R,M]."""
     X = _points(X, "X", spec.D)

@@ -206,16 +206,80 @@ class TrainableCGGP:
                     num_data=self.num_data)
 
 
+class _GPRLmlEstimate(torch.autograd.Function):
+    """Stochastic Lanczos estimate of log N(y | 0, K + s2 I) (`GPR.log_marginal_likelihood_estimate`) as an autograd
+    node over (variance, lengthscales, s2).  Backward, with alpha = Khat^-1 Y and W = Khat^-1 Z of the forward solve:
+
+        dLML/dtheta = 1/2 sum_p alpha_p^T dK alpha_p - 1/2 (P / t) sum_i (Khat^-1 z_i)^T dK z_i
+
+    -- one `mgp_kxx_grad` call with u = 1/2 [alpha, -(P/t) W] and v = [alpha, Z]; the s2 term is the same form with
+    dK = I, sum(u * v).  It is the Hutchinson estimate of the gradient (unbiased), not the exact derivative of the
+    fixed-probe value."""
+
+    @staticmethod
+    def forward(ctx, variance, lengthscales, s2, X, Y, probes, kind, cg):
+        from . import kernels
+        from .models import GPR
+        cls = {"se": kernels.SquaredExponential, "matern12": kernels.Matern12, "matern32": kernels.Matern32,
+               "matern52": kernels.Matern52}[kind]
+        kern = cls(variance=float(variance), lengthscales=[float(v) for v in lengthscales.reshape(-1)])
+        model = GPR((X, Y), kern, noise_variance=float(s2), conjugate_gradient=cg, solver="cg")
+        est, alpha, W, Z = model._lml_estimate(probes=probes)
+        P, t = Y.shape[1], Z.shape[1]
+        U = 0.5 * torch.cat([alpha, -(float(P) / t) * W], dim=1).contiguous()
+        V = torch.cat([alpha, Z], dim=1).contiguous()
+        ctx.spec, ctx.l_shape = kern.spec(X.shape[1]), lengthscales.shape
+        ctx.save_for_backward(X, U, V)
+        ctx.estimate = est
+        return torch.tensor(est.value, dtype=torch.float64)
+
+    @staticmethod
+    def backward(ctx, g):
+        X, U, V = ctx.saved_tensors
+        dvar, dls = ops.kxx_grad(ctx.spec, X, U, V)
+        ds2 = float((U * V).sum())
+        n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
+        gl = torch.tensor(dls if n_l > 1 else [sum(dls)], dtype=torch.float64).reshape(ctx.l_shape)
+        return (g * torch.tensor(dvar, dtype=torch.float64), g * gl, g * torch.tensor(ds2, dtype=torch.float64),
+                None, None, None, None, None)
+
+
 class TrainableGPR:
     """Exact GP regression with trainable kernel and noise (the `paper_cli_gpr.py` flow: L-BFGS on the marginal
-    likelihood).  `training_loss` is -log N(y | 0, K + s2 I) with K through `TrainableKernel.K` (`mgp_k_dense` forward,
-    `mgp_k_dense_vjp` backward) and a torch Cholesky; no probes (`num_probes = None`)."""
+    likelihood).
 
-    def __init__(self, kernel, noise_variance, X, Y):
+    `num_probes=None` (default): `training_loss` is -log N(y | 0, K + s2 I) with K through `TrainableKernel.K`
+    (`mgp_k_dense` forward, `mgp_k_dense_vjp` backward) and a torch Cholesky -- N x N memory.
+
+    `num_probes=t`: matrix-free at any N.  The value is `GPR.log_marginal_likelihood_estimate` with t Rademacher
+    probes (drawn once from `probe_seed`, fixed per model so repeated evaluations at one theta agree; `resample_probes`
+    draws new ones), solved by `conjugate_gradient` (default `ConjugateGradient(1e-8)`, from zero: Lanczos needs
+    x0 = 0, so there is no warm start).  The gradient comes from one `mgp_kxx_grad` call (`_GPRLmlEstimate`).  It is
+    an unbiased estimate of the true gradient, NOT the exact derivative of the fixed-probe value, so an L-BFGS line
+    search may see the two disagree: Adam is the tested optimiser here."""
+
+    def __init__(self, kernel, noise_variance, X, Y, *, num_probes=None, probe_seed=0, conjugate_gradient=None):
         self.kernel = TrainableKernel(kernel)
         self.likelihood_variance = Parameter(noise_variance)
         self.X, self.Y = X, Y
-        self.num_probes = None
+        self.num_probes = None if num_probes is None else int(num_probes)
+        if self.num_probes is not None and self.num_probes < 1:
+            raise ValueError("num_probes must be None or >= 1")
+        self.probe_seed = int(probe_seed)
+        self.conjugate_gradient = conjugate_gradient or ConjugateGradient(1e-8)
+        self.probes = None
+        if self.num_probes is not None:
+            self.resample_probes(self.probe_seed)
+
+    def resample_probes(self, seed=None):
+        """Draw a new fixed probe set [N, num_probes] (seeded CPU `torch.Generator`; `seed=None`: the next seed)."""
+        if self.num_probes is None:
+            raise ValueError("resample_probes needs num_probes")
+        self.probe_seed = self.probe_seed + 1 if seed is None else int(seed)
+        gen = torch.Generator().manual_seed(self.probe_seed)
+        z = torch.randint(0, 2, (self.X.shape[0], self.num_probes), generator=gen, dtype=torch.int64) * 2 - 1
+        self.probes = z.to(device=self.X.device, dtype=self.X.dtype)
+        return self.probes
 
     def parameters(self):
         return self.kernel.parameters() + [self.likelihood_variance.raw]
@@ -224,6 +288,17 @@ class TrainableGPR:
         X, Y = (self.X, self.Y) if data is None else data
         N, P = Y.shape
         s2 = self.likelihood_variance()
+        if self.num_probes is not None:
+            probes = self.probes if self.probes.shape[0] == N else None
+            if probes is None:  # another row count than the model's own data: a draw of that size
+                gen = torch.Generator().manual_seed(self.probe_seed)
+                probes = (torch.randint(0, 2, (N, self.num_probes), generator=gen, dtype=torch.int64) * 2 - 1).to(
+                    device=X.device, dtype=X.dtype)
+            ls = self.kernel.lengthscales_p()
+            if ls.dim() == 0:
+                ls = ls.reshape(1)
+            return _GPRLmlEstimate.apply(self.kernel.variance_p(), ls, s2, X.contiguous(), Y.contiguous(), probes,
+                                         self.kernel.name, self.conjugate_gradient)
         K = self.kernel.K(X) + s2.to(X.device) * torch.eye(N, dtype=X.dtype, device=X.device)
         L = torch.linalg.cholesky(K)
         v = torch.linalg.solve_triangular(L, Y, upper=False)
@@ -235,6 +310,9 @@ class TrainableGPR:
 
     def frozen_model(self):
         from .models import GPR
+        if self.num_probes is not None:
+            return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
+                       conjugate_gradient=self.conjugate_gradient, solver="cg")
         return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
                    solver="cholesky")
 
@@ -287,7 +365,7 @@ def train_using_lbfgs_and_update(data, model, max_num_iters, update_fn=None, upd
     sizes = [p.numel() for p in params]
     x, y = data
     probes = None
-    if model.num_probes is not None:
+    if model.num_probes is not None and hasattr(model, "Z"):  # TrainableGPR keeps its own fixed probes
         probes = rademacher((model.Z.shape[0], model.num_probes), model.Z.dtype, model.Z.device, probe_seed)
 
     def assign(flat):

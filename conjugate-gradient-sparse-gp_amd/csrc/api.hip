@@ -75,6 +75,9 @@ extern "C" int mgp_create(mgp_handle** out, int device) {
   const char* kx = getenv("MGP_KXX");
   if (kx && strcmp(kx, "plain") == 0) h->kxx_mode = 2;
   if (kx && strcmp(kx, "sym") == 0) h->kxx_mode = 1;
+  const char* kg = getenv("MGP_KXX_GRAD");
+  if (kg && strcmp(kg, "panel") == 0) h->kxx_grad_mode = 2;
+  if (kg && strcmp(kg, "fused") == 0) h->kxx_grad_mode = 0;
   const char* kxn = getenv("MGP_KXX_MIN_N");
   if (kxn && atol(kxn) >= 0) h->kxx_min_n = atol(kxn);
   const char* ns = getenv("MGP_NOSPLIT_PER_CU");
@@ -127,7 +130,8 @@ extern "C" size_t mgp_workspace_bytes(const mgp_handle* h) {
   if (h->pool) return h->pool_used;
   // 256 bytes of alignment slack per arena, as a fixed pool would spend
   return h->ws_bytes + h->cg_bytes + h->opws_bytes + h->gen_bytes + h->pack[0].bytes + h->pack[1].bytes +
-         h->tri_tab_bytes + h->prof_clk_bytes + h->kxx_bytes + 8 * 256 + (h->kxx ? 256 : 0);
+         h->tri_tab_bytes + h->prof_clk_bytes + h->kxx_bytes + h->kgrad_bytes + 8 * 256 + (h->kxx ? 256 : 0) +
+         (h->kgrad ? 256 : 0);
 }
 
 extern "C" int mgp_destroy(mgp_handle* h) {
@@ -141,6 +145,7 @@ extern "C" int mgp_destroy(mgp_handle* h) {
     if (h->opws) (void)hipFree(h->opws);
     if (h->gen) (void)hipFree(h->gen);
     if (h->kxx) (void)hipFree(h->kxx);
+    if (h->kgrad) (void)hipFree(h->kgrad);
     if (h->tri_tab) (void)hipFree(h->tri_tab);
     for (auto& ps : h->pack)
       if (ps.buf) (void)hipFree(ps.buf);

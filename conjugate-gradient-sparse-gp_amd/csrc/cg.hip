@@ -118,17 +118,19 @@ __global__ __launch_bounds__(NTB) void cg_update_kernel(const CgCtrl* __restrict
                                                         T* __restrict__ z, const T* __restrict__ ap,
                                                         T* __restrict__ rz, int* __restrict__ over,
                                                         T* __restrict__ err, long n, T thr, T min_float,
-                                                        PrecondDev pc, int mode, int force) {
+                                                        PrecondDev pc, int mode, int force,
+                                                        T* __restrict__ coef, long coef_steps) {
   if (!force && ctrl->active == 0) return;
   __shared__ T red[16];
   const long off = (long)blockIdx.x * n;
   const T rz_old = rz[blockIdx.x];
   const bool first = mode == 0 || mode == 1 || mode == 3;
+  T gamma = 0;
   if (first) {
     T d = 0;
     for (long j = threadIdx.x; j < n; j += blockDim.x) d = mgp_fma(p[off + j], ap[off + j], d);
     d = block_sum(d, red);
-    const T gamma = (d <= min_float) ? (T)0 : rz_old / d;
+    gamma = (d <= min_float) ? (T)0 : rz_old / d;
     for (long j = threadIdx.x; j < n; j += blockDim.x) {
       v[off + j] = mgp_fma(gamma, p[off + j], v[off + j]);
       if (mode != 1) r[off + j] = mgp_fma(-gamma, ap[off + j], r[off + j]);
@@ -157,6 +159,13 @@ __global__ __launch_bounds__(NTB) void cg_update_kernel(const CgCtrl* __restrict
   const bool drop = mode == 2 || mode == 5 || rz_old <= min_float;
   for (long j = threadIdx.x; j < n; j += blockDim.x) p[off + j] = drop ? zz[j] : mgp_fma(beta, p[off + j], zz[j]);
   if (threadIdx.x == 0) {
+    // recording solve (mode 0 only; the step index is the counter cg_advance_kernel moves after this launch)
+    if (coef != nullptr && mode == 0 && ctrl->iters < coef_steps) {
+      T* c = coef + ((long)ctrl->iters * gridDim.x + blockIdx.x) * 3;
+      c[0] = gamma;
+      c[1] = beta;
+      c[2] = (T)0.5 * s_rz;
+    }
     rz[blockIdx.x] = s_rz;
     err[blockIdx.x] = (T)0.5 * s_rz;
     over[blockIdx.x] = ((T)0.5 * s_rr > thr) ? 1 : 0;
@@ -174,7 +183,8 @@ __global__ __launch_bounds__(NT) void cg_update_fused_kernel(CgCtrl* __restrict_
                                                              int* __restrict__ over, T* __restrict__ err, long n,
                                                              T thr, T min_float, const T* __restrict__ dinv,
                                                              int max_it, int ap_slices, long ap_stride,
-                                                             const T* __restrict__ agree, int world) {
+                                                             const T* __restrict__ agree, int world,
+                                                             T* __restrict__ coef, long coef_steps) {
   // multi-rank SGPR operator: `ap` is the all-reduced partial itself and `agree` the word behind it -- the sum of
   // the ranks' gate words.  Unless every rank computed this application nobody uses it: the gate closes and all
   // ranks leave the loop on the same iteration (what finish_allreduce_kernel did in a launch of its own).
@@ -273,6 +283,16 @@ __global__ __launch_bounds__(NT) void cg_update_fused_kernel(CgCtrl* __restrict_
     }
   }
   if (t == 0) {
+    // recording solve: step index = the counter the last arriver below moves, read before this workgroup's ticket
+    if (coef != nullptr) {
+      const int it = ctrl->iters;
+      if (it < coef_steps) {
+        T* c = coef + ((long)it * gridDim.x + blockIdx.x) * 3;
+        c[0] = gamma;
+        c[1] = beta;
+        c[2] = (T)0.5 * s_rz;
+      }
+    }
     rz[blockIdx.x] = s_rz;
     err[blockIdx.x] = (T)0.5 * s_rz;
     __hip_atomic_store(&over[blockIdx.x], ((T)0.5 * s_rr > thr) ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -537,7 +557,7 @@ constexpr int kRetryWithoutPersist = 1;  // internal: never crosses the C ABI
 template <typename T>
 int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const T* B, const T* V0, long Bt,
                 double thr, long max_it, long cycle, double min_float, int check_every, T* V, T* err_out,
-                mgp_cg_stats* stats) {
+                mgp_cg_stats* stats, T* coef, long coef_steps) {
   const long n = op->n;
   const long tot = Bt * n;
   const auto t0 = std::chrono::steady_clock::now();
@@ -582,7 +602,7 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
                           : (!h->d1_persist_off && mgp_dense1_persist_eligible(h, n, 6)) ? 6
                                                                                          : (n <= 4096 ? 4 : 6));
   const bool dense1 = op->kind == MGP_OP_DENSE && Bt >= 1 && Bt <= d1_cols && !dense_pre &&
-                      pc.kind != MGP_PRE_BLOCK && cycle > max_it && mgp_dense1_eligible(h, n);
+                      pc.kind != MGP_PRE_BLOCK && cycle > max_it && mgp_dense1_eligible(h, n) && coef == nullptr;
   size_t bytes = (size_t)tot * sizeof(T) * (need_z ? 4 : 3) + (size_t)Bt * sizeof(T) + (size_t)Bt * sizeof(int) + 64 +
                  (dense1 ? mgp_dense1_bytes(h, op->dtype, n, Bt) : 0);
   MGP_TRY(mgp_reserve(h, &h->cg, &h->cg_bytes, bytes));
@@ -644,7 +664,7 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
     MGP_LAUNCH_CHECK(h);
     MGP_TRY(external_z(nullptr));
     MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz, over,
-                       err_out, n, (T)thr, (T)min_float, pc, 5, 1);
+                       err_out, n, (T)thr, (T)min_float, pc, 5, 1, (T*)nullptr, 0L);
     MGP_LAUNCH_CHECK(h);
   }
   if (!dense1) {
@@ -751,7 +771,7 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
 #define MGP_FUSED(EPTV, NTV)                                                                                   \
   hipLaunchKernelGGL((cg_update_fused_kernel<T, EPTV, NTV>), dim3((unsigned)Bt), dim3(NTV), 0, s, ctrl, V, r, p,    \
                      ap_src, rz, over, err_out, n, (T)thr, (T)min_float, dinv, (int)max_it, ap_slices, ap_stride, agree, \
-                     world)
+                     world, coef, coef_steps)
         switch (fused_ept) {
           case 1: MGP_FUSED(1, 256); break;
           case 2: MGP_FUSED(2, 256); break;
@@ -767,25 +787,25 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
       } else if (!reset) {
         if (!dense_pre) {
           MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 0, 0);
+                             over, err_out, n, (T)thr, (T)min_float, pc, 0, 0, coef, coef_steps);
         } else {
           MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 3, 0);
+                             over, err_out, n, (T)thr, (T)min_float, pc, 3, 0, (T*)nullptr, 0L);
           MGP_LAUNCH_CHECK(h);
           MGP_TRY(external_z(&ctrl->active));
           MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 4, 0);
+                             over, err_out, n, (T)thr, (T)min_float, pc, 4, 0, (T*)nullptr, 0L);
         }
       } else {
         MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                           over, err_out, n, (T)thr, (T)min_float, pc, 1, 0);
+                           over, err_out, n, (T)thr, (T)min_float, pc, 1, 0, (T*)nullptr, 0L);
         MGP_LAUNCH_CHECK(h);
         MGP_TRY(apply_operator<T>(h, op, V, Bt, ap, &ctrl->active));
         hipLaunchKernelGGL((cg_residual_kernel<T>), dim3(nblk(tot)), dim3(256), 0, s, ctrl, B, ap, r, tot, 0);
         MGP_LAUNCH_CHECK(h);
         if (dense_pre) MGP_TRY(external_z(&ctrl->active));
         MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                           over, err_out, n, (T)thr, (T)min_float, pc, dense_pre ? 5 : 2, 0);
+                           over, err_out, n, (T)thr, (T)min_float, pc, dense_pre ? 5 : 2, 0, (T*)nullptr, 0L);
       }
       MGP_LAUNCH_CHECK(h);
       hipLaunchKernelGGL(cg_advance_kernel, dim3(1), dim3(256), 0, s, ctrl, over, Bt, 1, (int)max_it);
@@ -818,10 +838,12 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
 
 }  // namespace
 
-extern "C" int mgp_pcg_solve(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B,
-                             const void* V0, int64_t Bt, double error_threshold, int64_t max_iterations,
-                             int64_t max_steps_cycle, double min_float, int32_t check_every, void* V_out,
-                             void* err_out, mgp_cg_stats* stats) {
+namespace {
+
+int pcg_solve_entry(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B, const void* V0,
+                    int64_t Bt, double error_threshold, int64_t max_iterations, int64_t max_steps_cycle,
+                    double min_float, int32_t check_every, void* V_out, void* err_out, mgp_cg_stats* stats, void* coef,
+                    int64_t coef_steps) {
   if (!h) return MGP_E_BADARG;
   MGP_TRY(check_operator(h, op));
   if (Bt < 0) return mgp_fail(h, MGP_E_SHAPE, "Bt < 0");
@@ -838,9 +860,11 @@ extern "C" int mgp_pcg_solve(mgp_handle* h, const mgp_operator* op, const mgp_pr
   auto run = [&]() -> int {
     if (op->dtype == MGP_F64)
       return pcg_solve_t<double>(h, op, pre, (const double*)B, (const double*)V0, Bt, error_threshold, max_iterations,
-                                 max_steps_cycle, min_float, check_every, (double*)V_out, (double*)err_out, stats);
+                                 max_steps_cycle, min_float, check_every, (double*)V_out, (double*)err_out, stats,
+                                 (double*)coef, coef_steps);
     return pcg_solve_t<float>(h, op, pre, (const float*)B, (const float*)V0, Bt, error_threshold, max_iterations,
-                              max_steps_cycle, min_float, check_every, (float*)V_out, (float*)err_out, stats);
+                              max_steps_cycle, min_float, check_every, (float*)V_out, (float*)err_out, stats,
+                              (float*)coef, coef_steps);
   };
   int rc = run();
   if (rc == kRetryWithoutPersist) {
@@ -854,6 +878,31 @@ extern "C" int mgp_pcg_solve(mgp_handle* h, const mgp_operator* op, const mgp_pr
     h->d1_persist_off = false;
   }
   return rc;
+}
+
+}  // namespace
+
+extern "C" int mgp_pcg_solve(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B,
+                             const void* V0, int64_t Bt, double error_threshold, int64_t max_iterations,
+                             int64_t max_steps_cycle, double min_float, int32_t check_every, void* V_out,
+                             void* err_out, mgp_cg_stats* stats) {
+  return pcg_solve_entry(h, op, pre, B, V0, Bt, error_threshold, max_iterations, max_steps_cycle, min_float,
+                         check_every, V_out, err_out, stats, nullptr, 0);
+}
+
+// Recording solve (stochastic Lanczos quadrature): the Eye-preconditioned update kernels write (gamma, beta, 0.5 rz)
+// of every step taken into coef[step, b]; the register-resident dense route is not taken (pcg_solve_t).
+extern "C" int mgp_pcg_solve_record(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B,
+                                    const void* V0, int64_t Bt, double error_threshold, int64_t max_iterations,
+                                    int64_t max_steps_cycle, double min_float, int32_t check_every, void* V_out,
+                                    void* err_out, mgp_cg_stats* stats, void* coef, int64_t coef_steps) {
+  if (!h) return MGP_E_BADARG;
+  if (pre != nullptr && pre->kind != MGP_PRE_EYE)
+    return mgp_fail(h, MGP_E_BADARG, "recording solve: only the identity preconditioner (MGP_PRE_EYE)");
+  if (coef == nullptr) return mgp_fail(h, MGP_E_BADARG, "recording solve: coef is NULL");
+  if (coef_steps < 0) return mgp_fail(h, MGP_E_BADARG, "recording solve: coef_steps < 0");
+  return pcg_solve_entry(h, op, pre, B, V0, Bt, error_threshold, max_iterations, max_steps_cycle, min_float,
+                         check_every, V_out, err_out, stats, coef, coef_steps);
 }
 
 extern "C" int mgp_operator_apply(mgp_handle* h, const mgp_operator* op, const void* P, int64_t Bt, void* out) {

@@ -31,6 +31,12 @@ struct mgp_handle {
   int kxx_mode = 0;  // mgp_kxx_matvec / MGP_OP_KXX_NOISE: 0 = symmetric kernel where it serves (fp64, D <= 32, N >=
                      // kxx_min_n), 1 = wherever it can (MGP_KXX=sym), 2 = the plain sweep mgp_sweep(X, X) + s2 V (MGP_KXX=plain)
   long kxx_min_n = 1L << 16;  // MGP_KXX_MIN_N
+  // hyper-parameter bilinear forms of k(X,X) (kxx_grad.hip): packed rows, packed columns, workgroup partials -- or,
+  // on the panel route, one row panel of G = U V^T
+  void* kgrad = nullptr;
+  size_t kgrad_bytes = 0;
+  int kxx_grad_mode = 0;  // mgp_kxx_grad: 0 = fused pair kernel where it serves (fp64, D <= 32; MGP_KXX_GRAD=fused),
+                          // 2 = row panels through mgp_k_dense_vjp everywhere (MGP_KXX_GRAD=panel)
   // generic-D scratch (transposed multipliers, kernel panel, chunk output)
   void* gen = nullptr;
   size_t gen_bytes = 0;

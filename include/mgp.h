@@ -201,6 +201,17 @@ int mgp_kmn_sq_colsum(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t
  * or 32 -- O(N), nothing N x N (N = 2^20, D = 32, R = 8: 904 MiB). */
 int mgp_kxx_matvec(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, const void* V, int32_t R,
                    int v_layout, void* out, int out_layout);
+/* Hyper-parameter bilinear forms of K = k(X, X) (no noise term): for theta = variance and each ARD lengthscale,
+ *   dvariance = sum_r u_r^T (dK/dvariance) v_r,   dlengthscales[d] = sum_r u_r^T (dK/dl_d) v_r   (host doubles)
+ * -- the gradient of the exact-GP marginal likelihood without dK/dtheta or any N x N matrix (callers fold weights into
+ * U).  U, V [N, R] (MGP_COLS) or [R, N] (MGP_ROWS), R >= 1.  Diagonal terms count (dk_ii/dvariance = 1, dk_ii/dl = 0).
+ * fp64, D <= MGP_FUSED_MAX_D: each unordered pair once with c_ij = sum_r (u_ri v_rj + u_rj v_ri), direct differences,
+ * workgroup partials added in a fixed order (csrc/kxx_grad.hip; two calls are bit-identical).  Scratch, one arena of
+ * the handle: 8 N' (D' + 2 C) + 64 CUs (D' + 1) bytes, N' = N rounded up to 256, D' = D rounded up to 4, 8, 16 or 32,
+ * C = 16 (8 for D' = 32 and Matern-1/2) -- O(N D).  fp32, D > 32 (or MGP_KXX_GRAD=panel in the environment): row panels of at most
+ * 256 MB of G = U[rows] V^T through mgp_k_dense_vjp.  N = 0 writes zeros.  Synchronises the stream. */
+int mgp_kxx_grad(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* U, const void* V, int32_t R,
+                 int layout, double* dvariance, double* dlengthscales);
 
 /* ---- dense symmetric product (row M2: `state.p @ A`, conjugate_gradient.py:65) ---------
  * out[Bt,n] = P[Bt,n] @ A[n,n] for SYMMETRIC A (CG requires it; computed as rows of A dotted
@@ -220,6 +231,16 @@ int mgp_pcg_solve(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre,
                   const void* V0, int64_t Bt, double error_threshold, int64_t max_iterations,
                   int64_t max_steps_cycle, double min_float, int32_t check_every, void* V_out,
                   void* err_out, mgp_cg_stats* stats);
+/* mgp_pcg_solve that also records, for every CG step k actually taken (steps gated off after convergence write
+ * nothing; k < coef_steps), coef[k, b, 0:3] = (gamma, beta, 0.5 rz after the step) in the operator's dtype -- the
+ * coefficients a stochastic Lanczos quadrature builds the Lanczos tridiagonal of column b from.  Preconditioner
+ * MGP_PRE_EYE (or NULL) only, else MGP_E_BADARG.  The record is defined up to the first residual refresh: pass
+ * max_steps_cycle > max_iterations.  Never takes the register-resident dense route.  coef [coef_steps, Bt, 3] device,
+ * coef_steps >= 0. */
+int mgp_pcg_solve_record(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B,
+                         const void* V0, int64_t Bt, double error_threshold, int64_t max_iterations,
+                         int64_t max_steps_cycle, double min_float, int32_t check_every, void* V_out,
+                         void* err_out, mgp_cg_stats* stats, void* coef, int64_t coef_steps);
 /* one application of an operator: out[Bt,n] = P[Bt,n] @ Op (used by tests and the bench) */
 int mgp_operator_apply(mgp_handle* h, const mgp_operator* op, const void* P, int64_t Bt, void* out);
 /* the matrix-free (Kmm + Lambda) product by name (row M2, `p @ A` with A = add_diagonal(Kuu, lambda),
