@@ -1228,7 +1228,7 @@ int symm_skinny_lds_launch(mgp_handle* h, const T* A, long n, const T* P, long B
     if (n >= 256 && h->skinny_pipe && (h->skinny_stagger <= 100 || h->skinny_stagger == 107)) {
       piped = true;
       const bool whole = (n % 64) == 0;
-      if (h->skinny_stagger == 107 && vec && whole)
+      if (h->skinny_stagger == 107 && vec && whole && ks > 1)  // the timeline lies behind the slice partials
         hipLaunchKernelGGL((symm_skinny_pipe_kernel<T, NBT, true, false, 5>), grid, dim3(512), 0, h->stream, A, n, P, Bt,
                            dst, kr_len, gate);
       else if (vec && whole)
@@ -1243,7 +1243,8 @@ int symm_skinny_lds_launch(mgp_handle* h, const T* A, long n, const T* P, long B
     }
   }
   if (piped) {
-  } else if (vec && h->skinny_stagger > 100 && NBT == 4 && std::is_same<T, double>::value) {  // diagnosis only
+  } else if (vec && h->skinny_stagger > 100 && (h->skinny_stagger <= 104 || ks > 1) && NBT == 4 &&
+             std::is_same<T, double>::value) {  // diagnosis only
 #define MGP_SK_ABL(V)                                                                                              \
   hipLaunchKernelGGL((symm_skinny_lds_kernel<T, NBT, KW, true, V>), grid, dim3(512), 0, h->stream, A, n, P, Bt, dst, \
                      kr_len, gate, 0)
@@ -1251,10 +1252,8 @@ int symm_skinny_lds_launch(mgp_handle* h, const T* A, long n, const T* P, long B
     else if (h->skinny_stagger == 102) MGP_SK_ABL(2);
     else if (h->skinny_stagger == 103) MGP_SK_ABL(3);
     else if (h->skinny_stagger == 104) MGP_SK_ABL(4);
-    else if (ks > 1) {
-      if (h->skinny_stagger == 105) MGP_SK_ABL(5);
-      else MGP_SK_ABL(6);
-    }
+    else if (h->skinny_stagger == 105) MGP_SK_ABL(5);
+    else MGP_SK_ABL(6);
 #undef MGP_SK_ABL
   } else if (vec)
     hipLaunchKernelGGL((symm_skinny_lds_kernel<T, NBT, KW, true>), grid, dim3(512), 0, h->stream, A, n, P, Bt, dst,

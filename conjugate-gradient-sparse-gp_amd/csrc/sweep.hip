@@ -846,7 +846,10 @@ int launch_sweep(mgp_handle* h, const SweepParams& prm, int D, const T* A, long 
   // D <= 16 -> 2 points, 512 threads; D <= 32 -> 2 points, 256 threads, 2048-entry table, one SGPR row copy
   // several right-hand sides: 2 owned points per lane (the RC accumulators per point take the registers), 512-thread form only
   const bool fast_on = kFastEligible && h->sweep_fast != 0 && (RC == 1 || h->sweep_fast == 2);
-  const int frpt = !fast_on ? 0 : (RC > 1 ? (DP > 16 ? 1 : ((RC <= 4 && DP <= 8) ? h->sweep_fast_rpt_rc : 2)) : (DP <= 8 ? h->sweep_fast_rpt : (DP > 16 ? h->sweep_fast_rpt32 : 2)));  // owned points per lane
+  // MGP_SWEEP_RPT selects among the 256-thread forms (MGP_SWEEP_FAST=1); the 512-thread form at D <= 8 exists with 4
+  // only, and the grid below must be sized for the kernel that is launched
+  const int rpt8 = h->sweep_fast == 2 ? 4 : h->sweep_fast_rpt;
+  const int frpt = !fast_on ? 0 : (RC > 1 ? (DP > 16 ? 1 : ((RC <= 4 && DP <= 8) ? h->sweep_fast_rpt_rc : 2)) : (DP <= 8 ? rpt8 : (DP > 16 ? h->sweep_fast_rpt32 : 2)));  // owned points per lane
   const int RPT = frpt ? frpt : TileCfg<DP>::RPT;
   const int fnt = (frpt && h->sweep_fast == 2 && DP <= 16) ? 512 : kThreads;
   const long per_block = (long)fnt * RPT;
