@@ -13,7 +13,13 @@ all-reduce of the [1, M] partial (N > 1), and the fused vector update -- all ins
 The rows of X are sharded over the ranks (strong scaling: N is the TOTAL row count).
 Inputs are resident in HBM before the timed region.
 
-`roofline` (dominant kernel: the fused sweep, a vector-ALU-issue-bound kernel -- DESIGN.md 4.1).  Every number
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line (`"full": false`):
+`roofline`, `cpu_baseline`, `convergence`, `convergence_preconditioned` and `cdgp_same_size` are null in it, and so
+are the entries of `iterations_to_threshold` and `time_to_solution_s`.  `--full` adds, after the timed steps, the
+profiled second pass behind `roofline` and the convergence, preconditioned-solve, CDGP and CPU-baseline legs
+(`--full --no-extra-legs`: the roofline pass alone).
+
+`roofline` (--full; dominant kernel: the fused sweep, a vector-ALU-issue-bound kernel -- DESIGN.md 4.1).  Every number
 can be recomputed from this line and ONE committed file, profiles/valu_issue_model.json (PMC, per config):
     busy  = pairs_per_launch / 64 * active_valu_quadcycles_per_wave_pair          [VALU-busy quad-cycles, all SIMDs]
     frac  = busy * 4 / (1024 SIMDs * 2.4e9 Hz) / avg_launch_s                     [issue-slot fraction, datasheet clock]
@@ -93,10 +99,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the profiled second pass "
+                         "behind `roofline`, and the convergence / preconditioned / CDGP / CPU-baseline legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline leg")
     ap.add_argument("--cpu-sample-rows", type=int, default=393216)  # ~13 s of host work on 16 cores
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo only to rehearse N>1 on one GPU)")
-    ap.add_argument("--convergence-cap", type=int, default=0, help="iteration cap of the convergence leg (0 = M)")
+    ap.add_argument("--convergence-cap", type=int, default=0,
+                    help="with --full: iteration cap of the convergence leg (0 = M)")
     ap.add_argument("--force-collective", action="store_true",
                     help="N=1 only: run the all-reduce hook on a 1-rank group (measures its fixed per-step cost)")
     ap.add_argument("--rows", type=int, default=0, help="override the TOTAL row count (0 = the config's)")
@@ -104,7 +114,8 @@ def main():
                     help="N=1 only: what ONE rank of a W-GPU run does per step -- N/W rows, the 1/W row slab of the "
                          "replicated Kmm.p term, the collective on a 1-rank communicator.  Timing only: the operator is "
                          "a rank's PARTIAL, so the legs that need the whole system are skipped")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the convergence / CDGP / CPU legs")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="with --full: skip the convergence / CDGP / CPU legs, keep the roofline pass")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="strong (default): the config's N is the TOTAL row count, sharded over the ranks -- the "
                          "size BASELINE.json's metric is quoted on; weak: every rank holds the config's N rows")
@@ -225,111 +236,113 @@ def main():
     # ---- dominant kernel: the fused sweep (K_nm.p and K_mn.u are the same kernel symbol).  A second pass of the
     # same K steps with HIP events bracketing every launch of it on the solve's stream; 16 workgroups of every
     # bracketed launch stamp the shader-clock and constant counters (mgp_profile_read_clocks)
-    hd = _hip.get_handle(dev)
-    clock = None
-    hd.check(hd.lib.mgp_profile_enable(hd.h, 1))
-    run_steps(args.steps)
-    launches = ctypes.c_int64(0)
-    each = (ctypes.c_double * (2 * args.steps + 8))()
-    hd.check(hd.lib.mgp_profile_read_each(hd.h, each, len(each), ctypes.byref(launches)))
-    cap = 16 * (2 * args.steps + 8)
-    mhz = (ctypes.c_double * cap)()
-    nclk = ctypes.c_int64(0)
-    if hd.lib.mgp_profile_read_clocks(hd.h, mhz, cap, ctypes.byref(nclk)) == 0 and nclk.value > 0:
-        c = np.array(mhz[:min(nclk.value, cap)], dtype=np.float64)
-        clock = {"mean_mhz": float(c.mean()), **{k + "_mhz": v for k, v in _pct(c).items()},
-                 "min_mhz": float(c.min()), "max_mhz": float(c.max()), "workgroups_sampled": int(nclk.value),
-                 "method": "up to 16 workgroups of every timed sweep launch stamp s_memrealtime (100 MHz) and s_memtime "
-                           "(shader clock) at their start and at the end of their loop; clock = ratio of the differences "
-                           "(mgp_profile_read_clocks)"}
-    hd.check(hd.lib.mgp_profile_enable(hd.h, 0))
-    durs = np.array(each[:min(launches.value, len(each))], dtype=np.float64)
-    sweep_ms = float(durs.mean()) if durs.size else float("nan")
-    sweep_pct = {k + "_ms": v for k, v in _pct(durs).items()} if durs.size else None
-    R = 1
-    pairs_launch = float(n_local) * M
-    bytes_launch = float(esize) * (n_local * D + M * D + M * R + n_local * R)
-    ach_gbps = bytes_launch / (sweep_ms * 1e-3) / 1e9
-    equiv_gemv_gbps = float(esize) * n_local * M / (sweep_ms * 1e-3) / 1e9
-    vector_peak = FP64_VECTOR_PEAK_TFLOPS if esize == 8 else FP32_VECTOR_PEAK_TFLOPS
-    flops_pair = EXECUTED_FLOPS_PER_PAIR.get((esize, kname), EXECUTED_FLOPS_PER_PAIR[(esize, "se")])(D, R)
-    tflops_exec = pairs_launch * flops_pair / (sweep_ms * 1e-3) / 1e12
+    roof = None
+    if args.full:
+        hd = _hip.get_handle(dev)
+        clock = None
+        hd.check(hd.lib.mgp_profile_enable(hd.h, 1))
+        run_steps(args.steps)
+        launches = ctypes.c_int64(0)
+        each = (ctypes.c_double * (2 * args.steps + 8))()
+        hd.check(hd.lib.mgp_profile_read_each(hd.h, each, len(each), ctypes.byref(launches)))
+        cap = 16 * (2 * args.steps + 8)
+        mhz = (ctypes.c_double * cap)()
+        nclk = ctypes.c_int64(0)
+        if hd.lib.mgp_profile_read_clocks(hd.h, mhz, cap, ctypes.byref(nclk)) == 0 and nclk.value > 0:
+            c = np.array(mhz[:min(nclk.value, cap)], dtype=np.float64)
+            clock = {"mean_mhz": float(c.mean()), **{k + "_mhz": v for k, v in _pct(c).items()},
+                     "min_mhz": float(c.min()), "max_mhz": float(c.max()), "workgroups_sampled": int(nclk.value),
+                     "method": "up to 16 workgroups of every timed sweep launch stamp s_memrealtime (100 MHz) and s_memtime "
+                               "(shader clock) at their start and at the end of their loop; clock = ratio of the differences "
+                               "(mgp_profile_read_clocks)"}
+        hd.check(hd.lib.mgp_profile_enable(hd.h, 0))
+        durs = np.array(each[:min(launches.value, len(each))], dtype=np.float64)
+        sweep_ms = float(durs.mean()) if durs.size else float("nan")
+        sweep_pct = {k + "_ms": v for k, v in _pct(durs).items()} if durs.size else None
+        R = 1
+        pairs_launch = float(n_local) * M
+        bytes_launch = float(esize) * (n_local * D + M * D + M * R + n_local * R)
+        ach_gbps = bytes_launch / (sweep_ms * 1e-3) / 1e9
+        equiv_gemv_gbps = float(esize) * n_local * M / (sweep_ms * 1e-3) / 1e9
+        vector_peak = FP64_VECTOR_PEAK_TFLOPS if esize == 8 else FP32_VECTOR_PEAK_TFLOPS
+        flops_pair = EXECUTED_FLOPS_PER_PAIR.get((esize, kname), EXECUTED_FLOPS_PER_PAIR[(esize, "se")])(D, R)
+        tflops_exec = pairs_launch * flops_pair / (sweep_ms * 1e-3) / 1e12
 
-    # PMC model of this config's kernel instantiation (committed; tools/make_valu_model.py builds it from the
-    # rocprofv3 --pmc passes of tools/pmc_sweep.sh)
-    model, model_src, model_stale = None, os.path.join("profiles", "valu_issue_model.json"), None
-    try:
-        model_file = json.load(open(os.path.join(ROOT, model_src)))
-        entries = model_file["configs"]
-        # the counters belong to ONE version of the kernel source: a later edit makes `frac` stale
-        import hashlib
-        model_stale = []
-        for path, sha in (model_file.get("measured_sources") or {}).items():
-            data = open(os.path.join(ROOT, path), "rb").read()
-            if hashlib.sha1(b"blob %d\0" % len(data) + data).hexdigest() != sha:
-                model_stale.append(path)
-        model = entries.get(args.config)
-        if model is None:  # another config that runs the same kernel instantiation (C2, C3r: the C3 kernel)
-            same = [e for e in entries.values()
-                    if (e.get("D"), e.get("dtype"), e.get("kernel_kind")) == (D, dtype_name, kname)]
-            model = same[0] if same else None
-    except Exception:
-        model = None
-    roof = {"bound": "valu",
-            "bound_note": "vector-ALU issue roofline: the kernel issues no MFMA (on MI355X the fp64 matrix and vector "
-                          "peaks are the same ALUs: measured and rejected, DESIGN.md 4.1) and is not HBM-bound (SURVEY 8d); "
-                          "the hbm figures BASELINE.json asks for are in the nested object",
-            "kernel": (f"sweep_fast_kernel<{D},{kname},RC=1,RPT=4,512 threads,2^13-entry table>" if esize == 8 and D <= 8
-                       else f"sweep_fast_kernel<{D},{kname},RC=1>" if esize == 8
-                       else f"sweep_kernel<float,{D},{kname},1>") + " (K_nm.p and K_mn.u are the same symbol)",
-            "unit": "G VALU quad-cycles/s", "peak": PEAK_GQUAD_PER_S,
-            "peak_note": "1024 SIMDs x 2.4e9 Hz / 4: one fp64-class VALU wave-instruction holds its SIMD for 4 cycles "
-                         "(SQ_ACTIVE_INST_VALU counts these quad-cycles; fp32 transcendentals count 2)"}
-    if model:
-        q = float(model["active_valu_quadcycles_per_wave_pair"])
-        busy = pairs_launch / 64.0 * q
-        roof["achieved"] = busy / (sweep_ms * 1e-3) / 1e9
-        roof["frac"] = roof["achieved"] / PEAK_GQUAD_PER_S
-        roof["model"] = {"file": model_src, "config": args.config,
-                         "active_valu_quadcycles_per_wave_pair": q,
-                         "valu_instructions_per_pair": model.get("valu_instructions_per_pair"),
-                         "pmc_source": model.get("source"), "kernel": model.get("kernel"),
-                         "stale": bool(model_stale),
-                         "stale_note": ("kernel sources edited since the PMC passes: " + ", ".join(model_stale)
-                                        if model_stale else "the PMC passes ran on the kernel sources of this tree "
-                                        "(git blob hashes in the model file)" if model_stale is not None else None),
-                         "recompute": "frac = pairs_per_launch / 64 * active_valu_quadcycles_per_wave_pair * 4 / "
-                                      "(1024 * 2.4e9) / (avg_launch_ms * 1e-3)"}
-        if clock:
-            roof["frac_at_sustained_clock"] = busy * 4.0 / (NUM_SIMDS * clock["mean_mhz"] * 1e6) / (sweep_ms * 1e-3)
-    else:
-        roof["achieved"] = None
-        roof["frac"] = None
-        roof["model"] = {"error": f"no entry for {args.config} in {model_src}"}
-    traffic = None
-    if model and model.get("hbm_bytes_per_launch") and not args.rows and not emu and world == 1:
-        traffic = float(model["hbm_bytes_per_launch"])
-    roof.update({
-        "sustained_clock": clock,
-        "avg_launch_ms": sweep_ms, "launches_timed": int(launches.value), "launch_percentiles": sweep_pct,
-        "pairs_per_launch": pairs_launch, "gpair_evals_per_s": pairs_launch / (sweep_ms * 1e-3) / 1e9,
-        "traffic": traffic,
-        "traffic_note": "HBM bytes per launch from PMC (FETCH_SIZE x 2 + WRITE_SIZE, gfx950 correction, separate --pmc "
-                        "passes), mean of the K_nm and K_mn launches; null for row counts the PMC passes did not run",
-        "flops": {"note": "secondary: flops the kernel EXECUTES per pair (instruction list, csrc/sweep.hip) over the "
-                          "vector peak of its dtype; <= the issue fraction because adds/muls/integer ops fill a slot with "
-                          "one flop or none", "executed_flop_per_pair": flops_pair, "tflops": tflops_exec,
-                  "peak_tflops": vector_peak, "frac": tflops_exec / vector_peak,
-                  "survey_model_flop_per_pair": SURVEY_FLOPS_PER_PAIR(D, R),
-                  "frac_at_survey_flop_count": pairs_launch * SURVEY_FLOPS_PER_PAIR(D, R) / (sweep_ms * 1e-3) / 1e12
-                                               / vector_peak,
-                  "survey_note": "SURVEY 8d prices a 20-instruction libm exp the kernel does not execute: a model, "
-                                 "not a bound (it exceeds 1)"},
-        "hbm": {"bound": "hbm", "achieved": ach_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": ach_gbps / HBM_PEAK_GBPS, "algorithmic_bytes_per_launch": bytes_launch,
-                "equiv_dense_gemv_GBps_derived": equiv_gemv_gbps}})
+        # PMC model of this config's kernel instantiation (committed; tools/make_valu_model.py builds it from the
+        # rocprofv3 --pmc passes of tools/pmc_sweep.sh)
+        model, model_src, model_stale = None, os.path.join("profiles", "valu_issue_model.json"), None
+        try:
+            model_file = json.load(open(os.path.join(ROOT, model_src)))
+            entries = model_file["configs"]
+            # the counters belong to ONE version of the kernel source: a later edit makes `frac` stale
+            import hashlib
+            model_stale = []
+            for path, sha in (model_file.get("measured_sources") or {}).items():
+                data = open(os.path.join(ROOT, path), "rb").read()
+                if hashlib.sha1(b"blob %d\0" % len(data) + data).hexdigest() != sha:
+                    model_stale.append(path)
+            model = entries.get(args.config)
+            if model is None:  # another config that runs the same kernel instantiation (C2, C3r: the C3 kernel)
+                same = [e for e in entries.values()
+                        if (e.get("D"), e.get("dtype"), e.get("kernel_kind")) == (D, dtype_name, kname)]
+                model = same[0] if same else None
+        except Exception:
+            model = None
+        roof = {"bound": "valu",
+                "bound_note": "vector-ALU issue roofline: the kernel issues no MFMA (on MI355X the fp64 matrix and vector "
+                              "peaks are the same ALUs: measured and rejected, DESIGN.md 4.1) and is not HBM-bound (SURVEY 8d); "
+                              "the hbm figures BASELINE.json asks for are in the nested object",
+                "kernel": (f"sweep_fast_kernel<{D},{kname},RC=1,RPT=4,512 threads,2^13-entry table>" if esize == 8 and D <= 8
+                           else f"sweep_fast_kernel<{D},{kname},RC=1>" if esize == 8
+                           else f"sweep_kernel<float,{D},{kname},1>") + " (K_nm.p and K_mn.u are the same symbol)",
+                "unit": "G VALU quad-cycles/s", "peak": PEAK_GQUAD_PER_S,
+                "peak_note": "1024 SIMDs x 2.4e9 Hz / 4: one fp64-class VALU wave-instruction holds its SIMD for 4 cycles "
+                             "(SQ_ACTIVE_INST_VALU counts these quad-cycles; fp32 transcendentals count 2)"}
+        if model:
+            q = float(model["active_valu_quadcycles_per_wave_pair"])
+            busy = pairs_launch / 64.0 * q
+            roof["achieved"] = busy / (sweep_ms * 1e-3) / 1e9
+            roof["frac"] = roof["achieved"] / PEAK_GQUAD_PER_S
+            roof["model"] = {"file": model_src, "config": args.config,
+                             "active_valu_quadcycles_per_wave_pair": q,
+                             "valu_instructions_per_pair": model.get("valu_instructions_per_pair"),
+                             "pmc_source": model.get("source"), "kernel": model.get("kernel"),
+                             "stale": bool(model_stale),
+                             "stale_note": ("kernel sources edited since the PMC passes: " + ", ".join(model_stale)
+                                            if model_stale else "the PMC passes ran on the kernel sources of this tree "
+                                            "(git blob hashes in the model file)" if model_stale is not None else None),
+                             "recompute": "frac = pairs_per_launch / 64 * active_valu_quadcycles_per_wave_pair * 4 / "
+                                          "(1024 * 2.4e9) / (avg_launch_ms * 1e-3)"}
+            if clock:
+                roof["frac_at_sustained_clock"] = busy * 4.0 / (NUM_SIMDS * clock["mean_mhz"] * 1e6) / (sweep_ms * 1e-3)
+        else:
+            roof["achieved"] = None
+            roof["frac"] = None
+            roof["model"] = {"error": f"no entry for {args.config} in {model_src}"}
+        traffic = None
+        if model and model.get("hbm_bytes_per_launch") and not args.rows and not emu and world == 1:
+            traffic = float(model["hbm_bytes_per_launch"])
+        roof.update({
+            "sustained_clock": clock,
+            "avg_launch_ms": sweep_ms, "launches_timed": int(launches.value), "launch_percentiles": sweep_pct,
+            "pairs_per_launch": pairs_launch, "gpair_evals_per_s": pairs_launch / (sweep_ms * 1e-3) / 1e9,
+            "traffic": traffic,
+            "traffic_note": "HBM bytes per launch from PMC (FETCH_SIZE x 2 + WRITE_SIZE, gfx950 correction, separate --pmc "
+                            "passes), mean of the K_nm and K_mn launches; null for row counts the PMC passes did not run",
+            "flops": {"note": "secondary: flops the kernel EXECUTES per pair (instruction list, csrc/sweep.hip) over the "
+                              "vector peak of its dtype; <= the issue fraction because adds/muls/integer ops fill a slot with "
+                              "one flop or none", "executed_flop_per_pair": flops_pair, "tflops": tflops_exec,
+                      "peak_tflops": vector_peak, "frac": tflops_exec / vector_peak,
+                      "survey_model_flop_per_pair": SURVEY_FLOPS_PER_PAIR(D, R),
+                      "frac_at_survey_flop_count": pairs_launch * SURVEY_FLOPS_PER_PAIR(D, R) / (sweep_ms * 1e-3) / 1e12
+                                                   / vector_peak,
+                      "survey_note": "SURVEY 8d prices a 20-instruction libm exp the kernel does not execute: a model, "
+                                     "not a bound (it exceeds 1)"},
+            "hbm": {"bound": "hbm", "achieved": ach_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": ach_gbps / HBM_PEAK_GBPS, "algorithmic_bytes_per_launch": bytes_launch,
+                    "equiv_dense_gemv_GBps_derived": equiv_gemv_gbps}})
 
-    extra = not args.no_extra_legs
+    extra = args.full and not args.no_extra_legs
     # ---- bounded convergence report (informational): real stopping rule, thr = 1e-6
     conv = None
     if extra and (rank == 0 or world > 1):
@@ -553,6 +566,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f64" if esize == 8 else "f32",
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": f"{args.config}: CG on S=s2(Kmm+jI)+KmnKnm, K_nm matrix-free, {kname} kernel",
                        "N": N, "D": D, "M": M, "rhs": 1, "rows_per_gpu": n_local,
                        "kmm_rows_of_this_rank": [int(kmm_rows[0]), int(kmm_rows[1])],

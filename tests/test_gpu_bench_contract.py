@@ -1,5 +1,5 @@
-"""The driver's contract for bench.py: one JSON line on stdout carrying the required keys, the
-roofline and cpu_baseline objects; run here at a reduced row count so it takes seconds."""
+"""The driver's contract for bench.py: one JSON line on stdout carrying the required keys; with --full also the
+roofline and cpu_baseline objects.  Run here at a reduced row count so it takes seconds."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup",
-                          "1", "--rows", "65536", "--convergence-cap", "8", "--cpu-sample-rows", "2048"],
+                          "1", "--rows", "65536", "--full", "--convergence-cap", "8", "--cpu-sample-rows", "2048"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -50,7 +50,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                           "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--rows", "65536",
-                          "--convergence-cap", "8", "--no-cpu-baseline"],
+                          "--full", "--convergence-cap", "8", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
@@ -72,7 +72,7 @@ def test_bench_rank_share_emulation():
     """`--emulate-world W`: one rank's share of a W-GPU step on the one GPU of the box (N/W rows, the 1/W slab of
     Kmm.p, the exchange on a one-rank libmgp communicator).  Timing only -- the other legs are skipped."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--emulate-world", "4", "--steps", "4",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -96,7 +96,7 @@ def test_bench_dump_outputs_are_the_timed_solve(tmp_path):
 
     def run(d):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
-                              "--warmup", "1", "--rows", "65536", "--no-extra-legs", "--dump-outputs", str(d)],
+                              "--warmup", "1", "--rows", "65536", "--full", "--no-extra-legs", "--dump-outputs", str(d)],
                              capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert out.returncode == 0, out.stderr[-2000:]
         d_line = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
@@ -110,3 +110,37 @@ def test_bench_dump_outputs_are_the_timed_solve(tmp_path):
         assert a[n].dtype == np.float64 and np.all(np.isfinite(a[n]))
         np.testing.assert_allclose(a[n], b[n], rtol=1e-12, atol=0)
     assert np.any(a["alpha"] != 0) and a["half_rz"][0, 0] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_timed_steps_alone(tmp_path):
+    """Without --full the run stops after the timed steps: the headline keys as with --full, every figure that needs
+    another pass or leg null, and --dump-outputs the same timed solve as a --full run of the same arguments."""
+    import numpy as np
+
+    def run(d, *extra):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                              "--warmup", "1", "--rows", "65536", "--dump-outputs", str(d), *extra],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, out.stdout[-2000:]
+        return json.loads(lines[0]), {n: np.load(os.path.join(d, n + ".npy")) for n in ("alpha", "half_rz")}
+
+    d, a = run(tmp_path / "plain")
+    f, b = run(tmp_path / "full", "--full", "--no-extra-legs")
+    assert d["full"] is False and f["full"] is True
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config"):
+        assert key in d, key
+    for key in ("metric", "unit", "n_gpus", "steps", "warmup", "higher_is_better", "scaling", "dtype", "data"):
+        assert d[key] == f[key], key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "CG iters/s" and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    for key in ("roofline", "cpu_baseline", "convergence", "convergence_preconditioned", "cdgp_same_size"):
+        assert d[key] is None, key
+    assert all(v is None for v in d["iterations_to_threshold"].values())
+    assert f["roofline"]["launches_timed"] == 6
+    for n in a:
+        assert a[n].dtype == np.float64 and a[n].shape == b[n].shape
+        np.testing.assert_allclose(a[n], b[n], rtol=1e-12, atol=0)
