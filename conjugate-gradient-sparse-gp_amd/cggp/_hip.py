@@ -123,6 +123,8 @@ SIGNATURES = {
     "mgp_kmm_lambda_matvec": (_I, [_P, _KP, _P, _L, _P, _P, _L, _P]),
     "mgp_kxx_matvec": (_I, [_P, _KP, _P, _L, _D, _P, ctypes.c_int32, _I, _P, _I]),
     "mgp_kxx_grad": (_I, [_P, _KP, _P, _L, _P, _P, ctypes.c_int32, _I, ctypes.POINTER(_D), ctypes.POINTER(_D)]),
+    "mgp_kmn_knm_vjp": (_I, [_P, _KP, _P, _L, _P, _L, _P, _P, _P, ctypes.c_int32, ctypes.POINTER(_D),
+                             ctypes.POINTER(_D), _P]),
     "mgp_pcg_solve_record": (_I, [_P, ctypes.POINTER(MgpOperator), ctypes.POINTER(MgpPrecond), _P, _P, _L, _D,
                                   _L, _L, _D, ctypes.c_int32, _P, _P, ctypes.POINTER(MgpCgStats), _P, _L]),
     # random Fourier features (cggp/rff.py)

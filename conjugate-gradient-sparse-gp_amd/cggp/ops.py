@@ -106,6 +106,36 @@ def kxx_grad(spec, X, U, V, layout=COLS):
     return dvar.value, [dls[d] for d in range(spec.D)]
 
 
+def kmn_knm_vjp(spec, X, Z, Gq, Y=None, Gb=None, need_dZ=False):
+    """VJP of (theta, Z) -> (Q, B) = (K_mn K_nm, K_mn Y), K = k(X, Z), at the cotangents Gq [M, M] (need not be
+    symmetric) and Gb [M, P]: (dvariance: float, [dl_d for d < D], dZ [M, D] or None).  Nothing N x M beyond one row
+    panel is formed (`mgp_kmn_knm_vjp`).  fp64 and D <= 32 only: libmgp refuses anything else (MgpError)."""
+    X = _points(X, "X", spec.D)
+    Z = _points(Z, "Z", spec.D, X.dtype)
+    N, M = X.shape[0], Z.shape[0]
+    if M < 1:
+        raise ValueError("kmn_knm_vjp needs M >= 1")
+    Gq = _hip.check_tensor(Gq, "Gq", dtype=X.dtype, shape=(M, M))
+    if (Y is None) != (Gb is None):
+        raise ValueError("Y and Gb go together")
+    P = 0
+    if Y is not None:
+        Y = _hip.check_tensor(Y, "Y", dtype=X.dtype)
+        if Y.dim() != 2 or Y.shape[0] != N:
+            raise ValueError(f"Y must be [N={N}, P], got {tuple(Y.shape)}")
+        P = Y.shape[1]
+        Gb = _hip.check_tensor(Gb, "Gb", dtype=X.dtype, shape=(M, P))
+    dZ = torch.empty((M, spec.D), dtype=X.dtype, device=X.device) if need_dZ else None
+    dvar = ctypes.c_double(0.0)
+    dls = (ctypes.c_double * _hip.MGP_MAX_D)()
+    hd = _hip.get_handle(X.device)
+    k = spec.struct(_hip.dtype_code(X))
+    hd.check(hd.lib.mgp_kmn_knm_vjp(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(Gq),
+                                    _hip.ptr(Y if P else None), _hip.ptr(Gb if P else None), P, ctypes.byref(dvar),
+                                    dls, _hip.ptr(dZ)))
+    return dvar.value, [dls[d] for d in range(spec.D)], dZ
+
+
 def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e-16, check_every=10):
     """CG from zero on `op` (a `conjugate_gradient.LinearOperator`) for the rows of rhs [Bt, n], identity
     preconditioner, no residual refresh, recording every step taken (`mgp_pcg_solve_record`).

@@ -317,13 +317,206 @@ class TrainableGPR:
                    solver="cholesky")
 
 
+def sgpr_bound(Kmm_j, Q, b, yy, s2, variance, N):
+    """Titsias' collapsed bound (GPflow `SGPR.elbo`, as `models.SGPR.elbo` forms it) as a torch function of the [M, M]
+    quantities: Kmm_j = k(Z, Z) + jitter I, Q = K_mn K_nm, b = K_mn y [M, 1], yy = y^T y, s2 the noise variance,
+    `variance` the kernel variance (the trace term), N the number of data rows."""
+    L = torch.linalg.cholesky(Kmm_j)
+    T1 = torch.linalg.solve_triangular(L, Q, upper=False)
+    AAT = torch.linalg.solve_triangular(L, T1.t(), upper=False) / s2  # A A^T = L^-1 Q L^-T / s2
+    B = AAT + torch.eye(Q.shape[0], dtype=Q.dtype, device=Q.device)
+    LB = torch.linalg.cholesky(B)
+    Aerr = torch.linalg.solve_triangular(L, b, upper=False) / torch.sqrt(s2)
+    c = torch.linalg.solve_triangular(LB, Aerr, upper=False) / torch.sqrt(s2)
+    const = -0.5 * N * math.log(2.0 * math.pi)
+    logdet = -torch.log(LB.diagonal()).sum() - 0.5 * N * torch.log(s2)
+    quad = -0.5 * yy / s2 + 0.5 * (c * c).sum()
+    trace = -0.5 * N * variance / s2 + 0.5 * AAT.diagonal().sum()
+    return const + logdet + quad + trace
+
+
+def sgpr_bound_adjoints(Kmm_j, Q, b, yy, s2, variance, N):
+    """Value and adjoints of `sgpr_bound` (step 1 of the SGPR gradient: [M, M] work only, two Choleskys and triangular
+    solves), by torch autograd on the device of the inputs: (value: float, Gq = dL/dQ, Gb = dL/db, G_Kmm = dL/dKmm_j,
+    d_s2, d_variance) -- the last two the direct derivatives (floats).  Gq need not be symmetric."""
+    dev, dt = Q.device, Q.dtype
+    # leaves made here, not views of them: this also runs inside a backward pass, where grad mode is off
+    as_t = lambda v: (v.detach().to(device=dev, dtype=dt) if isinstance(v, torch.Tensor)
+                      else torch.tensor(float(v), dtype=dt, device=dev)).reshape(()).clone().requires_grad_(True)
+    Kt, Qt, bt = (t.detach().clone().requires_grad_(True) for t in (Kmm_j, Q, b))
+    s2t, vt = as_t(s2), as_t(variance)
+    yyt = torch.as_tensor(float(yy), dtype=dt, device=dev)
+    with torch.enable_grad():
+        val = sgpr_bound(Kt, Qt, bt, yyt, s2t, vt, float(N))
+        gK, gQ, gb, gs2, gv = torch.autograd.grad(val, [Kt, Qt, bt, s2t, vt])
+    return float(val.detach()), gQ, gb, gK, float(gs2), float(gv)
+
+
+def _profile_grad(name, r2):
+    """df/dr2 of f = k / variance at the scaled squared distance (csrc/grad.hip's forms; Matern-1/2: 0 below GPflow's
+    1e-36 floor)."""
+    if name == "se":
+        return -0.5 * torch.exp(-0.5 * r2)
+    floor = ~(r2 > 1e-36)
+    r = torch.sqrt(torch.where(floor, torch.full_like(r2, 1e-36), r2))
+    zero = torch.zeros_like(r2)
+    if name == "matern12":
+        return torch.where(floor, zero, -torch.exp(-r) / (2.0 * r))
+    if name == "matern32":
+        s3 = math.sqrt(3.0)
+        return torch.where(floor, zero, -1.5 * torch.exp(-s3 * r))
+    s5 = math.sqrt(5.0)
+    return torch.where(floor, zero, (-5.0 / 6.0) * (1.0 + s5 * r) * torch.exp(-s5 * r))
+
+
+def kmm_grad_z(name, variance, lengthscales, Z, G, max_elems=1 << 24):
+    """dL/dZ [M, D] through Kmm = k(Z, Z) (+ a constant jitter) given G = dL/dKmm: row i collects
+    sum_j (G_ij + G_ji) dk(z_i, z_j)/dz_i, direct differences, rows in chunks of at most `max_elems` M D temporaries."""
+    ls = torch.as_tensor(lengthscales, dtype=Z.dtype, device=Z.device).reshape(-1)
+    A = Z / ls
+    S = G + G.t()
+    M, D = Z.shape
+    out = torch.empty_like(Z)
+    step = max(1, max_elems // max(1, M * D))
+    for i0 in range(0, M, step):
+        diff = A[i0:i0 + step, None, :] - A[None, :, :]
+        fp = _profile_grad(name, (diff * diff).sum(dim=2))
+        out[i0:i0 + step] = ((S[i0:i0 + step] * fp)[:, :, None] * diff).sum(dim=1)
+    return out * (2.0 * float(variance) / ls)
+
+
+class _SGPRElbo(torch.autograd.Function):
+    """`models.SGPR.elbo` as an autograd node over (variance, lengthscales, s2, Kmm_j, Z).  Forward: Q by
+    `mgp_kmn_knm`, b by `mgp_kmn_matvec`, y^T y, summed over ranks with `allreduce`, then `sgpr_bound`.  Backward:
+    `sgpr_bound_adjoints`; the Kmm_j cotangent goes back to the caller (`TrainableKernel.K`, whose backward is
+    `mgp_k_dense_vjp`) and, for a trainable Z, through `kmm_grad_z`; the N-sized part is one `mgp_kmn_knm_vjp` call,
+    and its [dvariance, dl, dZ] partials are summed over ranks by ONE all-reduce."""
+
+    @staticmethod
+    def forward(ctx, variance, lengthscales, s2, Kmm_j, Z, model, X, Y):
+        D = X.shape[1]
+        spec = ops.KernelSpec(model.kernel.name, float(variance), [float(v) for v in lengthscales.reshape(-1)], D)
+        Zd = Z.detach()
+        Q = ops.kmn_knm(spec, X, Zd)
+        b = ops.kmn_matvec(spec, X, Zd, Y)
+        yy = ops.dot_all(Y, Y)
+        if model.allreduce is not None:
+            model.allreduce(Q.view(-1))
+            model.allreduce(b.view(-1))
+            t = torch.tensor([yy], dtype=torch.float64, device=X.device)
+            model.allreduce(t)
+            yy = t.item()
+        dev = X.device
+        s2d = s2.detach().to(device=dev, dtype=X.dtype)
+        vd = variance.detach().to(device=dev, dtype=X.dtype)
+        value = sgpr_bound(Kmm_j.detach(), Q, b, yy, s2d, vd, float(model.num_data))
+        ctx.spec, ctx.model, ctx.yy = spec, model, yy
+        ctx.v_shape, ctx.l_shape, ctx.s_shape = variance.shape, lengthscales.shape, s2.shape
+        ctx.save_for_backward(Kmm_j.detach(), Q, b, s2d, vd, Zd, X, Y)
+        return value.detach().cpu()
+
+    @staticmethod
+    def backward(ctx, g):
+        Kmm_j, Q, b, s2d, vd, Zd, X, Y = ctx.saved_tensors
+        model, spec = ctx.model, ctx.spec
+        g = float(g)
+        _, Gq, Gb, GK, ds2, dvar = sgpr_bound_adjoints(Kmm_j, Q, b, ctx.yy, s2d, vd, model.num_data)
+        need_z = ctx.needs_input_grad[4]
+        D, M = spec.D, Zd.shape[0]
+        nv, nl, nz = ops.kmn_knm_vjp(spec, X, Zd, Gq.contiguous(), Y, Gb.contiguous(), need_dZ=need_z)
+        if model.allreduce is not None:  # this rank's rows only: one all-reduce of [dvariance, dl, dZ]
+            parts = [torch.tensor([nv] + list(nl), dtype=torch.float64, device=X.device)]
+            if need_z:
+                parts.append(nz.reshape(-1))
+            buf = torch.cat(parts)
+            model.allreduce(buf)
+            nv, nl = float(buf[0]), buf[1:1 + D].tolist()
+            if need_z:
+                nz = buf[1 + D:].reshape(M, D)
+        gv = torch.tensor(g * (dvar + nv), dtype=torch.float64).reshape(ctx.v_shape)
+        n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
+        gl = torch.tensor([g * v for v in nl] if n_l > 1 else [g * sum(nl)], dtype=torch.float64).reshape(ctx.l_shape)
+        gs = torch.tensor(g * ds2, dtype=torch.float64).reshape(ctx.s_shape)
+        gZ = None
+        if need_z:
+            gZ = g * (nz + kmm_grad_z(spec.kind, spec.variance, spec.lengthscales, Zd, GK))
+        return gv, gl, gs, g * GK, gZ, None, None, None
+
+
+class TrainableSGPR:
+    """SGPR (Titsias' collapsed bound, `models.SGPR`) with trainable kernel variance / lengthscales, noise variance
+    and, with `trainable_inducing=True`, inducing inputs Z (the reference's `--tip`: `set_trainable(
+    model.inducing_variable, tip)`, `paper_cli_geospatial.py:237`).  The model holds its data (`internal_data`):
+    `train_using_adam_and_update` takes one full-data step per iteration (`cggp/optimize.py:215-216`).
+
+    `elbo()` equals `models.SGPR(...).elbo()` at the same values and is an autograd node (`_SGPRElbo`) whose backward
+    needs nothing N x M: one `mgp_kmn_knm_vjp` call for the N-sized part.  With `allreduce` (same contract as
+    `models.SGPR`: X, Y are this rank's rows) the forward sums Q, K_mn y and y^T y over ranks and the backward makes one
+    all-reduce of its N-sized partials, so every rank ends with the same gradient.  fp64, D <= 32, Y [N, 1]."""
+
+    num_probes = None
+    internal_data = True
+
+    def __init__(self, kernel, noise_variance, X, Y, Z, *, jitter=1e-6, trainable_inducing=False, allreduce=None,
+                 num_data=None, conjugate_gradient=None):
+        for name, t in (("X", X), ("Y", Y), ("Z", Z)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ValueError(f"TrainableSGPR needs fp64 tensors: {name} is "
+                                 f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != X.shape[1]:
+            raise ValueError(f"X [N, D] and Z [M, D] expected, got {tuple(X.shape)} and {tuple(Z.shape)}")
+        if X.shape[1] > 32:
+            raise ValueError(f"TrainableSGPR needs D <= 32, got D={X.shape[1]}")
+        if Y.dim() != 2 or Y.shape != (X.shape[0], 1):
+            raise ValueError(f"Y must be [N={X.shape[0]}, 1], got {tuple(Y.shape)}")
+        self.kernel = kernel if isinstance(kernel, TrainableKernel) else TrainableKernel(kernel)
+        self.noise_p = Parameter(noise_variance)
+        self.X, self.Y = X.contiguous(), Y.contiguous()
+        self.trainable_inducing = bool(trainable_inducing)
+        self.Z = Z.detach().clone().contiguous().requires_grad_(self.trainable_inducing)
+        self.jitter = float(jitter)
+        self.allreduce = allreduce
+        if num_data is None:  # global row count, as models.SGPR agrees it
+            num_data = self.X.shape[0]
+            if allreduce is not None:
+                t = torch.tensor([float(num_data)], dtype=torch.float64, device=self.X.device)
+                allreduce(t)
+                num_data = int(round(t.item()))
+        self.num_data = int(num_data)
+        self.conjugate_gradient = conjugate_gradient or ConjugateGradient(1e-6)
+
+    def parameters(self):
+        ps = self.kernel.parameters() + [self.noise_p.raw]
+        return ps + [self.Z] if self.trainable_inducing else ps
+
+    def elbo(self, data=None):
+        X, Y = (self.X, self.Y) if data is None else (data[0].contiguous(), data[1].contiguous())
+        ls = self.kernel.lengthscales_p()
+        if ls.dim() == 0:
+            ls = ls.reshape(1)
+        Kmm_j = self.kernel.K(self.Z.detach(), jitter=self.jitter)
+        return _SGPRElbo.apply(self.kernel.variance_p(), ls, self.noise_p(), Kmm_j, self.Z, self, X, Y)
+
+    def training_loss(self, data=None, probes=None):
+        return -self.elbo(data)
+
+    def frozen_model(self):
+        from .models import SGPR
+        return SGPR((self.X, self.Y), self.kernel.frozen(), self.Z.detach().clone(), self.noise_p.value,
+                    self.conjugate_gradient, jitter=self.jitter, allreduce=self.allreduce, num_data=self.num_data)
+
+
 def train_using_adam_and_update(data, model, iterations, batch_size, learning_rate, update_fn=None,
                                 update_during_training=None, monitor=None, seed=0):
     """`cggp/optimize.py:198-254`: shuffled minibatches, one Adam step per iteration, optional
-    inducing-parameter update after each step, monitor callback per iteration."""
-    x, y = data
-    n = x.shape[0]
-    gen = torch.Generator().manual_seed(seed)
+    inducing-parameter update after each step, monitor callback per iteration.  A model with `internal_data` (SGPR)
+    takes one full-data `training_loss()` per step instead (`:215-216`); `data` and `batch_size` are then unused."""
+    # models that hold their data (SGPR) take one full-data step per iteration, no minibatch draw (:215-216)
+    internal = getattr(model, "internal_data", False)
+    if not internal:
+        x, y = data
+        n = x.shape[0]
+        gen = torch.Generator().manual_seed(seed)
     opt = torch.optim.Adam(model.parameters(), lr=learning_rate)
     update_during_training = update_during_training and (update_fn is not None)
 
@@ -331,14 +524,25 @@ def train_using_adam_and_update(data, model, iterations, batch_size, learning_ra
         update_fn()
     if monitor is not None:
         monitor(0)
-    perm, pos = torch.randperm(n, generator=gen), 0
+    if not internal:
+        perm, pos = torch.randperm(n, generator=gen), 0
     losses = []
     for iteration in range(iterations):
+        opt.zero_grad()
+        if internal:
+            loss = model.training_loss()
+            loss.backward()
+            opt.step()
+            losses.append(float(loss))
+            if update_during_training:
+                update_fn()
+            if monitor is not None:
+                monitor(iteration)
+            continue
         if pos + batch_size > n:
             perm, pos = torch.randperm(n, generator=gen), 0
         idx = perm[pos:pos + batch_size].to(x.device)
         pos += batch_size
-        opt.zero_grad()
         loss = model.training_loss((x[idx], y[idx]))
         loss.backward()
         opt.step()

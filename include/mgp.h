@@ -212,6 +212,26 @@ int mgp_kxx_matvec(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N,
  * 256 MB of G = U[rows] V^T through mgp_k_dense_vjp.  N = 0 writes zeros.  Synchronises the stream. */
 int mgp_kxx_grad(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* U, const void* V, int32_t R,
                  int layout, double* dvariance, double* dlengthscales);
+/* VJP of (theta, Z) -> (Q, B) = (K_mn K_nm, K_mn Y), K = k(X, Z) [N, M], at the cotangents Gq [M, M] and Gb [M, P]
+ * -- the N-sized part of the gradient of Titsias' collapsed bound (GPflow SGPR.elbo, which depends on the data only
+ * through Q, K_mn y and y^T y); mgp_k_dense_vjp would need the [N, M] cotangent W = K (Gq + Gq^T) + Y Gb^T.  Returns
+ *   dvariance = sum_nm W_nm dk_nm/dvariance,  dlengthscales[d] = sum_nm W_nm dk_nm/dl_d     (host doubles, ARD)
+ *   dZ[m, d]  = sum_n  W_nm dk_nm/dz_md                                                     ([M, D] device, row-major)
+ * Y [N, P] and Gb may be NULL with P = 0; dZ may be NULL (not computed).  Gq need not be symmetric: Gq + Gq^T is used.
+ * fp64 only (fp32: MGP_E_DTYPE), D <= MGP_FUSED_MAX_D (else MGP_E_BADARG), N >= 0, M >= 1, P >= 0; N = 0 writes zeros.
+ * dk/dr2 as mgp_k_dense_vjp forms it, r2 from direct differences; Matern-1/2 adds 0 to the lengthscales and to dZ
+ * below GPflow's r2 floor of 1e-36 (a data row equal to an inducing point gives no NaN).  Row panels of at most 256 MiB
+ * of K: k(X_panel, Z) (direct differences), W_panel by the fp64 MFMA NT GEMM, then one pair kernel reduces W_panel against
+ * the kernel's derivatives into workgroup partials that are added in a fixed order (csrc/kmn_grad.hip): no float
+ * atomics, two calls are bit-identical, and the results for row shards of X (and Y) add up to the whole up to
+ * rounding.  Scratch, one arena of the handle (counted by mgp_workspace_bytes, MGP_E_NOMEM from a fixed pool that is
+ * too small): 16 R M + 8 M^2 + 8 (4 CUs + B) (D' + 1) + (dZ ? 8 M D' (4 CUs / B + 2) : 0) + 2048 bytes, R = the
+ * panel rows (min(N, 2^25 / M) rounded down to 16, at least 16), B = ceil(M / 256), D' = D rounded up to 4, 8, 16
+ * or 32 -- at most 512 MiB + 8 M^2 + O(CUs (M + 256) D'), nothing N x M beyond one row panel.  Synchronises the
+ * stream. */
+int mgp_kmn_knm_vjp(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
+                    const void* Gq, const void* Y, const void* Gb, int32_t P, double* dvariance, double* dlengthscales,
+                    void* dZ);
 
 /* ---- dense symmetric product (row M2: `state.p @ A`, conjugate_gradient.py:65) ---------
  * out[Bt,n] = P[Bt,n] @ A[n,n] for SYMMETRIC A (CG requires it; computed as rows of A dotted

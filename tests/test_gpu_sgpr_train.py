@@ -1,0 +1,221 @@
+"""SGPR training on the MI355X: `mgp_kmn_knm_vjp` (the N-sized VJP of (K_mn K_nm, K_mn Y)) against long double, its
+determinism, shard additivity, empty input and refusals, and a 2^17-row case against existing pieces;
+`training.TrainableSGPR` against `models.SGPR.elbo` and autograd of the explicit-K bound, Adam and L-BFGS training,
+the frozen model, and a 2-rank sharded evaluation."""
+
+import os
+import socket
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from sgpr_grad_reference import kmn_knm_vjp_reference, sgpr_elbo_explicit
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "conjugate-gradient-sparse-gp_amd")
+KERNELS = ["se", "matern12", "matern32", "matern52"]
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def _vjp_inputs(N, M, D, P, seed, dup=0):
+    rng = np.random.default_rng(seed)
+    X = rng.uniform(-1.5, 1.5, (N, D))
+    Z = rng.uniform(-1.5, 1.5, (M, D))
+    if dup:
+        X[:dup] = Z[:dup]  # data rows equal to inducing points: r = 0
+    Gq = rng.standard_normal((M, M))
+    Y = rng.standard_normal((N, P)) if P else None
+    Gb = rng.standard_normal((M, P)) if P else None
+    return X, Z, Gq, Y, Gb
+
+
+# (kernel, D, N, M, P, dZ, duplicate rows)
+CASES = [("se", 1, 777, 37, 1, True, 0), ("se", 3, 5000, 130, 0, True, 0), ("se", 8, 777, 300, 3, False, 0),
+         ("se", 17, 1, 37, 1, True, 0), ("se", 32, 777, 130, 1, True, 0), ("matern12", 3, 777, 37, 1, True, 20),
+         ("matern12", 8, 5000, 1, 1, True, 0), ("matern32", 3, 777, 130, 3, True, 0),
+         ("matern32", 32, 1, 300, 0, True, 0), ("matern32", 17, 5000, 37, 1, False, 0),
+         ("matern52", 3, 777, 37, 1, True, 20), ("matern52", 8, 777, 300, 1, True, 0),
+         ("matern52", 1, 5000, 130, 3, True, 0), ("matern12", 17, 777, 300, 0, False, 0),
+         ("se", 8, 1, 1, 3, True, 0)]
+
+
+@pytest.mark.parametrize("name,D,N,M,P,want_dz,dup", CASES)
+def test_kmn_knm_vjp_against_long_double(name, D, N, M, P, want_dz, dup):
+    from cggp import ops
+    X, Z, Gq, Y, Gb = _vjp_inputs(N, M, D, P, N + 7 * M + D, dup)
+    ls = np.linspace(0.7, 1.3, D)
+    spec = ops.KernelSpec(name, 1.4, list(ls), D)
+    dv, dl, dZ = ops.kmn_knm_vjp(spec, t(X), t(Z), t(Gq), None if Y is None else t(Y), None if Gb is None else t(Gb),
+                                 need_dZ=want_dz)
+    rv, rl, rz, sv, sl, sz = kmn_knm_vjp_reference(name, 1.4, ls, X, Z, Gq, Y, Gb)
+    assert np.isfinite(dv) and np.all(np.isfinite(dl))
+    assert abs(dv - float(rv)) <= 1e-10 * float(sv)
+    assert np.all(np.abs(np.array(dl) - rl.astype(np.float64)) <= 1e-10 * sl.astype(np.float64))
+    if want_dz:
+        dZ = dZ.cpu().numpy()
+        assert np.all(np.isfinite(dZ))
+        assert np.all(np.abs(dZ - rz.astype(np.float64)) <= 1e-10 * sz.astype(np.float64) + 1e-300)
+    else:
+        assert dZ is None
+
+
+def test_kmn_knm_vjp_determinism_shards_empty_and_refusals():
+    from cggp import _hip, ops
+    X, Z, Gq, Y, Gb = _vjp_inputs(6001, 130, 5, 1, 3)
+    spec = ops.KernelSpec("matern32", 0.9, [0.8, 1.0, 1.1, 0.9, 1.2], 5)
+    Xt, Zt, Gqt, Yt, Gbt = t(X), t(Z), t(Gq), t(Y), t(Gb)
+    a = ops.kmn_knm_vjp(spec, Xt, Zt, Gqt, Yt, Gbt, need_dZ=True)
+    b = ops.kmn_knm_vjp(spec, Xt, Zt, Gqt, Yt, Gbt, need_dZ=True)
+    assert a[0] == b[0] and a[1] == b[1] and torch.equal(a[2], b[2])
+    s = 2345  # uneven shards add up to the whole
+    p = ops.kmn_knm_vjp(spec, Xt[:s], Zt, Gqt, Yt[:s], Gbt, need_dZ=True)
+    q = ops.kmn_knm_vjp(spec, Xt[s:], Zt, Gqt, Yt[s:], Gbt, need_dZ=True)
+    assert abs(p[0] + q[0] - a[0]) <= 1e-12 * abs(a[0])
+    assert np.max(np.abs(np.add(p[1], q[1]) - a[1])) <= 1e-12 * np.max(np.abs(a[1]))
+    assert float((p[2] + q[2] - a[2]).abs().max()) <= 1e-12 * float(a[2].abs().max())
+    e = ops.kmn_knm_vjp(spec, Xt[:0], Zt, Gqt, Yt[:0], Gbt, need_dZ=True)
+    assert e[0] == 0.0 and e[1] == [0.0] * 5 and float(e[2].abs().max()) == 0.0
+    with pytest.raises(_hip.MgpError, match="fp64"):
+        ops.kmn_knm_vjp(spec, Xt.float(), Zt.float(), Gqt.float())
+    spec33 = ops.KernelSpec("se", 1.0, [1.0], 33)
+    with pytest.raises(_hip.MgpError, match="D = 33"):
+        ops.kmn_knm_vjp(spec33, t(np.zeros((4, 33))), t(np.zeros((3, 33))), t(np.zeros((3, 3))))
+
+
+def test_kmn_knm_vjp_at_2e17_rows_against_existing_pieces():
+    from cggp import ops
+    N, M, D = 1 << 17, 1024, 8
+    X, Z, Gq, Y, Gb = _vjp_inputs(N, M, D, 1, 11)
+    spec = ops.KernelSpec("se", 1.1, list(np.linspace(0.8, 1.6, D)), D)
+    Xt, Zt, Gqt, Yt, Gbt = t(X), t(Z), t(Gq), t(Y), t(Gb)
+    dv, dl, dZ = ops.kmn_knm_vjp(spec, Xt, Zt, Gqt, Yt, Gbt, need_dZ=True)
+    K = ops.k_dense(spec, Xt, Zt)  # [N, M], 1 GiB
+    W = K @ (Gqt + Gqt.t()) + Yt @ Gbt.t()
+    rv, rl = ops.k_dense_vjp(spec, Xt, Zt, W)
+    assert abs(dv - rv) <= 1e-10 * abs(rv)
+    assert np.max(np.abs(np.array(dl) - rl)) <= 1e-10 * np.max(np.abs(rl))
+    del K
+    ls = torch.tensor(spec.lengthscales, dtype=torch.float64, device=DEV)
+    A, B = Xt / ls, Zt / ls
+    ref = torch.zeros_like(Zt)
+    for i0 in range(0, N, 8192):  # dZ_md = sum_n W_nm dk/dr2 * -2 (a - b)_d / l_d, chunked
+        diff = A[i0:i0 + 8192, None, :] - B[None, :, :]
+        fp = -0.5 * spec.variance * torch.exp(-0.5 * (diff * diff).sum(dim=2))
+        ref += ((W[i0:i0 + 8192] * fp)[:, :, None] * diff).sum(dim=0)
+    ref *= -2.0 / ls
+    assert float((dZ - ref).abs().max()) <= 1e-10 * float(ref.abs().max())
+
+
+def _sgpr_problem(N=1500, M=40, D=3, seed=5):
+    rng = np.random.default_rng(seed)
+    X = rng.uniform(-2.0, 2.0, (N, D))
+    Y = np.sin(1.5 * X[:, :1]) * np.cos(X[:, 1:2]) + 0.1 * rng.standard_normal((N, 1))
+    Z = X[rng.choice(N, M, replace=False)] + 0.01 * rng.standard_normal((M, D))
+    return X, Y, Z
+
+
+def _kernel(name, D):
+    from cggp import kernels
+    cls = {"se": kernels.SquaredExponential, "matern12": kernels.Matern12, "matern32": kernels.Matern32,
+           "matern52": kernels.Matern52}[name]
+    return cls(variance=1.2, lengthscales=list(np.linspace(0.8, 1.2, D)))
+
+
+@pytest.mark.parametrize("name", KERNELS)
+def test_trainable_sgpr_value_and_gradient(name):
+    from cggp import models, training
+    X, Y, Z = _sgpr_problem()
+    m = training.TrainableSGPR(_kernel(name, 3), 0.3, t(X), t(Y), t(Z), trainable_inducing=True)
+    loss = m.training_loss()
+    ref_model = models.SGPR((t(X), t(Y)), _kernel(name, 3), t(Z), 0.3, jitter=1e-6)
+    ref = -ref_model.elbo()
+    assert abs(float(loss.detach()) - ref) <= 1e-12 * abs(ref)
+    loss.backward()
+    ps = m.parameters()
+    got = [ps[0].grad, ps[1].grad, ps[2].grad, ps[3].grad.cpu()]
+    cpu = lambda a: torch.tensor(a, dtype=torch.float64)
+    raws = [p.detach().cpu().clone().requires_grad_() for p in ps]
+    f = torch.nn.functional.softplus
+    val = -sgpr_elbo_explicit(name, f(raws[0])[0], f(raws[1]), f(raws[2])[0], cpu(X), cpu(Y), raws[3], 1e-6)
+    want = torch.autograd.grad(val, raws)
+    for g, w in zip(got, want):
+        assert float((g - w).abs().max()) <= 1e-7 * float(w.abs().max()), (g, w)
+
+
+def test_trainable_sgpr_adam_lbfgs_and_frozen_model():
+    from cggp import models, training
+    X, Y, Z = _sgpr_problem(seed=9)
+    m = training.TrainableSGPR(_kernel("matern32", 3), 0.5, t(X), t(Y), t(Z), trainable_inducing=True)
+    start = float(m.training_loss())
+    Z0 = m.Z.detach().clone()
+    losses = training.train_using_adam_and_update(None, m, iterations=30, batch_size=None, learning_rate=0.05)
+    assert losses[-1] < start and float(m.training_loss()) < start
+    assert float((m.Z.detach() - Z0).abs().max()) > 1e-3
+    m2 = training.TrainableSGPR(_kernel("se", 3), 0.5, t(X), t(Y), t(Z))
+    start2 = float(m2.training_loss())
+    training.train_using_lbfgs_and_update((m2.X, m2.Y), m2, 10)
+    assert float(m2.training_loss()) < start2
+    fm = m.frozen_model()
+    fresh = models.SGPR((t(X), t(Y)), m.kernel.frozen(), m.Z.detach().clone(), m.noise_p.value, jitter=1e-6)
+    mu, var = fm.predict_f(t(X[:64]))
+    mu2, var2 = fresh.predict_f(t(X[:64]))
+    assert torch.equal(mu, mu2) and torch.equal(var, var2)
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _shard_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, PKG)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import torch.distributed as dist
+
+    from cggp import parallel, training
+    dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+    try:
+        X, Y, Z = _sgpr_problem()
+        lo, hi = (0, 611) if rank == 0 else (611, X.shape[0])  # uneven rows
+        ar = parallel.make_allreduce()
+        m = training.TrainableSGPR(_kernel("matern52", 3), 0.3, t(X[lo:hi]), t(Y[lo:hi]), t(Z),
+                                   trainable_inducing=True, allreduce=ar)
+        loss = m.training_loss()
+        loss.backward()
+        if rank == 0:
+            q.put((float(loss), [p.grad.detach().cpu().numpy().copy() for p in m.parameters()]))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_trainable_sgpr_two_ranks_on_one_gpu():
+    from cggp import training
+    ctx = mp.get_context("spawn")
+    q = ctx.SimpleQueue()
+    port = _free_port()
+    procs = [ctx.Process(target=_shard_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    loss2, grads2 = q.get()
+    for p in procs:
+        p.join(300)
+        assert p.exitcode == 0
+    X, Y, Z = _sgpr_problem()
+    m = training.TrainableSGPR(_kernel("matern52", 3), 0.3, t(X), t(Y), t(Z), trainable_inducing=True)
+    loss = m.training_loss()
+    loss.backward()
+    assert abs(loss2 - float(loss)) <= 1e-10 * abs(float(loss))
+    for g2, p in zip(grads2, m.parameters()):
+        g = p.grad.detach().cpu().numpy()
+        assert np.max(np.abs(g2 - g)) <= 1e-10 * np.max(np.abs(g))
