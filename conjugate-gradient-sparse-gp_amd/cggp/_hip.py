@@ -18,7 +18,7 @@ MGP_COMM_ID_BYTES = 128
 F32, F64 = 0, 1
 SE, MATERN12, MATERN32, MATERN52 = 0, 1, 2, 3
 COLS, ROWS = 0, 1
-PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK = 0, 1, 2, 3, 4
+PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK, PRE_LOWRANK = 0, 1, 2, 3, 4, 5
 OP_DENSE, OP_SGPR, OP_KMM_LAMBDA, OP_KXX_NOISE = 0, 1, 2, 3
 
 KERNEL_KINDS = {"se": SE, "matern12": MATERN12, "matern32": MATERN32, "matern52": MATERN52}
@@ -127,6 +127,8 @@ SIGNATURES = {
                              ctypes.POINTER(_D), _P]),
     "mgp_pcg_solve_record": (_I, [_P, ctypes.POINTER(MgpOperator), ctypes.POINTER(MgpPrecond), _P, _P, _L, _D,
                                   _L, _L, _D, ctypes.c_int32, _P, _P, ctypes.POINTER(MgpCgStats), _P, _L]),
+    "mgp_kxx_pivchol": (_I, [_P, _KP, _P, _L, ctypes.c_int32, _D, _P, _P, _P, ctypes.POINTER(ctypes.c_int32)]),
+    "mgp_lowrank_apply": (_I, [_P, _I, _P, _P, _L, _L, _P, _L, _P]),
     # random Fourier features (cggp/rff.py)
     "mgp_rff_features": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, _L]),
     "mgp_rff_sample": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, ctypes.c_int32, _D, _P, _I]),

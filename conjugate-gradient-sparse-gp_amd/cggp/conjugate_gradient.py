@@ -9,6 +9,7 @@ Same names, argument order and shapes as the reference:
   max_steps_cycle=None)`; `__call__(matrix[n,n], rhs[n,Bt], initial_solution=None) -> [n,Bt]`
   (reference :160-212)
 * `CGPreconditioner / EyePreconditioner / BlockPreconditioner`     (reference :125-157)
+* `PivotedCholeskyPreconditioner(rank, rel_tol)`: build-side addition for `KxxNoiseOperator` (exact GPR)
 
 The loop itself (`cg_step`, the stopping rule, the breakdown guards, the residual refresh)
 runs in libmgp (`csrc/cg.hip`); this module only validates, lays tensors out and wires the
@@ -487,6 +488,138 @@ class SubsampledNormalPreconditioner(DensePreconditioner):
         Pinv = torch.cholesky_inverse(L)
         self.sample_rows = int(n_tot)
         super().__init__((0.5 * (Pinv + Pinv.t())).to(operator.dtype).contiguous())
+
+
+class PivotedCholeskyPreconditioner(CGPreconditioner):
+    """P = L^T L + D with L [k, N] the rank-k partial pivoted Cholesky factor of K = k(X, X) and D = s2 I: the
+    standard preconditioner of the exact-GP system K + s2 I (Harbrecht et al. 2012; Gardner et al. 2018).  Build-side
+    addition, opt-in: `ConjugateGradient(thr, preconditioner=PivotedCholeskyPreconditioner())`.
+
+    P^-1 = D^-1 - B^T B with B = C^-1 L D^-1 and C C^T = I_k + L D^-1 L^T (Woodbury), O(N k) per application;
+    log|P| = 2 sum log C_ii + sum log D in closed form; z = L^T g1 + sqrt(D) g2 is a draw from N(0, P).
+
+    Inside the device CG loop it is libmgp's `MGP_PRE_LOWRANK` kind.  The factor (`mgp_kxx_pivchol`, matrix-free) is
+    built for a `KxxNoiseOperator` on first use, cached, and rebuilt when the operator's kernel parameters, noise or
+    `X` change; any other operator is a `TypeError`.  `rank_` holds the rank reached (`rel_tol` may stop the factor
+    early).  It pays where K has a low-rank part -- low-dimensional inputs, smooth kernels -- and does nothing for
+    high-dimensional inputs with short lengthscales.  `set_factor(L, D)` installs a hand-made factor
+    (any device, also the CPU: `__call__`, `log_det` and `sample` are plain torch)."""
+
+    def __init__(self, rank=128, rel_tol=1e-10):
+        self.rank = int(rank)
+        if not 1 <= self.rank <= 1024:
+            raise ValueError("rank must be in [1, 1024]")
+        self.rel_tol = float(rel_tol)
+        if not 0.0 <= self.rel_tol < 1.0:
+            raise ValueError("rel_tol must be in [0, 1)")
+        self.rank_ = None
+        self.L = self.D = self.diag_inv = self.B = self.piv = None
+        self._log_det = None
+        self._key = self._key_ref = None
+        self._normals = None
+
+    def set_factor(self, L, D):
+        """P = diag(D) + L^T L from a given L [k, n] and positive D (a number or [n])."""
+        n = L.shape[1]
+        D = torch.as_tensor(D, dtype=L.dtype, device=L.device)
+        D = D.expand(n).contiguous() if D.dim() == 0 else D.reshape(n).contiguous()
+        if not bool((D > 0).all()):
+            raise ValueError("D must be positive")
+        self.L, self.D = L.contiguous(), D
+        self.diag_inv = (1.0 / D).contiguous()
+        k = L.shape[0]
+        LD = self.L * self.diag_inv[None, :]
+        M = torch.eye(k, dtype=L.dtype, device=L.device) + LD @ self.L.t()
+        C = torch.linalg.cholesky(0.5 * (M + M.t()))
+        # B = C^-1 (L D^-1) through the explicit k x k inverse of the triangular factor and one GEMM: a triangular solve
+        # with n right-hand sides is not served by the BLAS at n = 2^17 (cond(C) = sqrt(cond(I + L D^-1 L^T)), harmless)
+        Cinv = torch.linalg.solve_triangular(C, torch.eye(k, dtype=L.dtype, device=L.device), upper=False)
+        self.B = (Cinv @ LD).contiguous()
+        self._log_det = float(2.0 * torch.log(C.diagonal()).sum() + torch.log(D).sum())
+        self.rank_ = k
+        self._key = None
+        return self
+
+    def _prepare(self, op):
+        """Build (or reuse) the factor of a `KxxNoiseOperator`; a factor given through `set_factor` stays."""
+        if self.L is not None and self._key is None:
+            if self.L.shape[1] != op.shape[0]:
+                raise ValueError(f"the factor has n={self.L.shape[1]}, the operator n={op.shape[0]}")
+            return
+        if not isinstance(op, KxxNoiseOperator):
+            raise TypeError("PivotedCholeskyPreconditioner builds its factor for a KxxNoiseOperator (K + s2 I of exact "
+                            f"GP regression) only, got {type(op).__name__}; use set_factor(L, D) for another matrix")
+        if op.dtype != torch.float64:
+            raise TypeError("PivotedCholeskyPreconditioner needs an fp64 operator (the factor is fp64 only)")
+        if not op.noise_variance > 0.0:
+            raise ValueError("PivotedCholeskyPreconditioner needs noise_variance > 0")
+        X = op.X
+        key = (id(X), X._version, tuple(X.shape), op.spec.kind, op.spec.variance, tuple(op.spec.lengthscales),
+               op.noise_variance, self.rank, self.rel_tol)
+        if key == self._key:
+            return
+        L, piv, _ = ops.kxx_pivchol(op.spec, X, self.rank, self.rel_tol)
+        self.set_factor(L, op.noise_variance)
+        self.piv = piv
+        self._key, self._key_ref = key, X  # the reference keeps id(X) from being reused
+
+    def _native(self, op):
+        self._prepare(op)
+        if self.B.dtype != op.dtype or self.B.device != op.device:
+            raise ValueError("the factor and the operator differ in dtype or device")
+        st = _hip.MgpPrecond()
+        if self.rank_ == 0:  # nothing low-rank found (rel_tol stopped at once): P = D
+            st.kind = _hip.PRE_JACOBI
+            st.diag_inv = self.diag_inv.data_ptr()
+            return st, (self.diag_inv,)
+        st.kind = _hip.PRE_LOWRANK
+        st.diag_inv = self.diag_inv.data_ptr()
+        st.dense_inv = self.B.data_ptr()
+        st.num_blocks = self.rank_
+        return st, (self.diag_inv, self.B)
+
+    def _require(self):
+        if self.B is None:
+            raise RuntimeError("no factor yet: solve with a KxxNoiseOperator first, or call set_factor(L, D)")
+
+    def solve(self, vec):
+        """P^-1 applied to the rows of vec [Bt, n]: `mgp_lowrank_apply` on the GPU, torch elsewhere."""
+        self._require()
+        if vec.is_cuda and self.rank_ > 0:
+            return ops.lowrank_apply(self.diag_inv, self.B, vec.contiguous())
+        return vec * self.diag_inv[None, :] - (vec @ self.B.t()) @ self.B
+
+    def __call__(self, vec, mat):
+        if self.B is None or (self._key is not None and isinstance(mat, KxxNoiseOperator)):
+            self._prepare(as_operator(mat))
+        z = vec * self.diag_inv[None, :] - (vec @ self.B.t()) @ self.B
+        return z, (z * vec).sum(dim=-1, keepdim=True)
+
+    def log_det(self):
+        """log|P| = 2 sum log C_ii + sum log D (= ... + N log s2 for the exact-GP system)."""
+        self._require()
+        return self._log_det
+
+    def sample(self, t, generator=None, seed=0):
+        """Z [n, t] = L^T g1 + sqrt(D) g2 with g1 [rank, t], g2 [n, t] standard normal from a seeded CPU
+        `torch.Generator` (`generator`, or one made from `seed`), so E[Z Z^T] / t = P.  With `seed` the normals are
+        drawn once for (seed, n, t) and for the full `rank`, so a rebuilt factor re-forms Z from the same draws."""
+        self._require()
+        n, t = self.L.shape[1], int(t)
+        if generator is not None:
+            g2 = torch.randn((n, t), generator=generator, dtype=torch.float64)
+            g1 = torch.randn((self.rank, t), generator=generator, dtype=torch.float64)
+        else:
+            nk = (int(seed), n, t, self.rank)
+            if self._normals is None or self._normals[0] != nk:
+                gen = torch.Generator().manual_seed(int(seed))
+                g2 = torch.randn((n, t), generator=gen, dtype=torch.float64)
+                g1 = torch.randn((self.rank, t), generator=gen, dtype=torch.float64)
+                self._normals = (nk, g1.to(self.L.device), g2.to(self.L.device))
+            g1, g2 = self._normals[1], self._normals[2]
+        g1 = g1.to(device=self.L.device, dtype=self.L.dtype)[:self.rank_]
+        g2 = g2.to(device=self.L.device, dtype=self.L.dtype)
+        return self.L.t() @ g1 + torch.sqrt(self.D)[:, None] * g2
 
 
 # --------------------------------------------------------------------------- solver

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .conjugate_gradient import ConjugateGradient, KxxNoiseOperator, SgprNormalOperator, SubsampledNormalPreconditioner
+from .conjugate_gradient import (ConjugateGradient, KxxNoiseOperator, PivotedCholeskyPreconditioner, SgprNormalOperator,
+                                 SubsampledNormalPreconditioner)
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
 from .slq import slq_log_quadratic
@@ -807,37 +808,60 @@ class GPR:
         seeded CPU `torch.Generator`, or `probes`), each normalised to unit norm so that the model's `error_threshold`
         acts per column and relative, records its step lengths and direction ratios (`ops.pcg_solve_record`).
         alpha = (K + s2 I)^-1 Y gives the data fit; the probe columns' Lanczos tridiagonals give
-        log|K + s2 I| ~= (1/t) sum_i |z_i|^2 e1^T log(T_i) e1 (stochastic Lanczos quadrature, `cggp.slq`)."""
+        log|K + s2 I| ~= (1/t) sum_i |z_i|^2 e1^T log(T_i) e1 (stochastic Lanczos quadrature, `cggp.slq`).
+
+        When the model's CG carries a `PivotedCholeskyPreconditioner` P the recording solve is preconditioned: the
+        probes are `P.sample(t, seed=seed)` (draws from N(0, P)), each probe's weight is z^T P^-1 z and
+        log_det = log|P| + the mean of the per-probe terms.  `probes` given by the caller are then taken as draws
+        with E[z z^T] = P -- the caller's duty; without the preconditioner they keep E[z z^T] = I."""
         return self._lml_estimate(num_probes, seed, probes)[0]
 
     def _lml_estimate(self, num_probes=15, seed=0, probes=None, conjugate_gradient=None):
-        """(LMLEstimate, alpha [N, P], (K + s2 I)^-1 Z [N, t], Z [N, t])."""
+        """(LMLEstimate, alpha [N, P], (K + s2 I)^-1 Z [N, t], Z [N, t]) -- with a `PivotedCholeskyPreconditioner` on
+        the CG the last entry is P^-1 Z, the right-hand factor of the gradient's trace term
+        E[(Khat^-1 z)^T dK (P^-1 z)] (`training._GPRLmlEstimate`)."""
         self._sync()
         X, Y = self.data
         N, P = Y.shape
+        cg = conjugate_gradient or self.conjugate_gradient
+        pre = cg.preconditioner if isinstance(cg.preconditioner, PivotedCholeskyPreconditioner) else None
+        if pre is not None:
+            pre._prepare(self.operator())
         if probes is None:
-            gen = torch.Generator().manual_seed(int(seed))
-            probes = torch.randint(0, 2, (N, int(num_probes)), generator=gen, dtype=torch.int64) * 2 - 1
+            if pre is not None:
+                probes = pre.sample(int(num_probes), seed=int(seed))
+            else:
+                gen = torch.Generator().manual_seed(int(seed))
+                probes = torch.randint(0, 2, (N, int(num_probes)), generator=gen, dtype=torch.int64) * 2 - 1
         probes = probes.to(device=X.device, dtype=X.dtype)
         if probes.dim() != 2 or probes.shape[0] != N or probes.shape[1] < 1:
             raise ValueError(f"probes must be [N={N}, t >= 1], got {tuple(probes.shape)}")
         t = probes.shape[1]
-        cg = conjugate_gradient or self.conjugate_gradient
         B = torch.cat([Y, probes], dim=1).t().contiguous()  # [P + t, N]: the solve's rows are the columns
         norms = torch.linalg.vector_norm(B, dim=1, keepdim=True)
         scale = torch.where(norms > 0, norms, torch.ones_like(norms))
-        sol, _, stats, coef = ops.pcg_solve_record(
-            self.operator(), B / scale, cg.error_threshold, cg.max_iterations, cg.min_float, cg.check_every)
+        if pre is None:
+            sol, _, stats, coef = ops.pcg_solve_record(
+                self.operator(), B / scale, cg.error_threshold, cg.max_iterations, cg.min_float, cg.check_every)
+            weights, right, log_det_p = norms[P:, 0] ** 2, probes, 0.0
+        else:
+            # preconditioned CG is Lanczos on P^-1/2 Khat P^-1/2 started at P^-1/2 z: the quadrature weight of a probe
+            # is z^T P^-1 z, and with E[z z^T] = P the mean estimates log|Khat| - log|P|
+            sol, _, stats, coef = ops.pcg_solve_record(
+                self.operator(), B / scale, cg.error_threshold, cg.max_iterations, cg.min_float, cg.check_every,
+                preconditioner=pre)
+            PiZ = pre.solve(B[P:])  # [t, N]
+            weights, right, log_det_p = (B[P:] * PiZ).sum(dim=1), PiZ.t(), pre.log_det()
         sol = sol * scale
         alpha, W = sol[:P].t(), sol[P:].t()
-        quads, _ = slq_log_quadratic(coef[:, P:, :].cpu().numpy(), (norms[P:, 0] ** 2).cpu().numpy(),
+        quads, _ = slq_log_quadratic(coef[:, P:, :].cpu().numpy(), weights.cpu().numpy(),
                                      cg.error_threshold, cg.min_float)
-        log_det = float(np.mean(quads))
+        log_det = log_det_p + float(np.mean(quads))
         std_error = float(np.std(quads, ddof=1) / math.sqrt(t)) if t > 1 else float("nan")
         data_fit = float((Y * alpha).sum())
         value = -0.5 * data_fit - 0.5 * P * log_det - 0.5 * N * P * math.log(2.0 * math.pi)
         est = LMLEstimate(value, log_det, data_fit, std_error, int(stats.iterations), bool(stats.converged))
-        return est, alpha, W, probes
+        return est, alpha, W, right
 
     def maximum_log_likelihood_objective(self):
         return self.log_marginal_likelihood()

@@ -136,9 +136,53 @@ def kmn_knm_vjp(spec, X, Z, Gq, Y=None, Gb=None, need_dZ=False):
     return dvar.value, [dls[d] for d in range(spec.D)], dZ
 
 
-def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e-16, check_every=10):
-    """CG from zero on `op` (a `conjugate_gradient.LinearOperator`) for the rows of rhs [Bt, n], identity
-    preconditioner, no residual refresh, recording every step taken (`mgp_pcg_solve_record`).
+def kxx_pivchol(spec, X, max_rank, rel_tol=0.0):
+    """Rank-`max_rank` partial pivoted Cholesky of K = k(X, X) (no noise), matrix-free (`mgp_kxx_pivchol`): greedy
+    pivots on the residual diagonal, stopping early once its sum is <= rel_tol * N * variance.  fp64 only.
+
+    Returns (L [rank, N] with K ~= L^T L, piv [rank] int64, diag [N] = the residual diagonal)."""
+    X = _points(X, "X", spec.D)
+    N = X.shape[0]
+    max_rank = int(max_rank)
+    if not 1 <= max_rank <= 1024:
+        raise ValueError(f"max_rank must be in [1, 1024], got {max_rank}")
+    rows = min(max_rank, N)
+    L = torch.empty((rows, N), dtype=X.dtype, device=X.device)
+    piv = torch.empty((rows,), dtype=torch.int64, device=X.device)
+    diag = torch.empty((N,), dtype=X.dtype, device=X.device)
+    rank = ctypes.c_int32(0)
+    if N > 0:
+        hd = _hip.get_handle(X.device)
+        k = spec.struct(_hip.dtype_code(X))
+        hd.check(hd.lib.mgp_kxx_pivchol(hd.h, ctypes.byref(k), _hip.ptr(X), N, max_rank, float(rel_tol), _hip.ptr(L),
+                                        _hip.ptr(piv), _hip.ptr(diag), ctypes.byref(rank)))
+    return L[:rank.value], piv[:rank.value], diag
+
+
+def lowrank_apply(diag_inv, B, R):
+    """Z [Bt, n] = diag_inv * R - (R @ B^T) @ B for R [Bt, n], B [k, n], diag_inv [n] (`mgp_lowrank_apply`): one
+    application of the diagonal-plus-low-rank preconditioner `MGP_PRE_LOWRANK`."""
+    R = _hip.check_tensor(R, "R")
+    if R.dim() != 2:
+        raise ValueError(f"R must be [Bt, n], got {tuple(R.shape)}")
+    Bt, n = R.shape
+    B = _hip.check_tensor(B, "B", dtype=R.dtype)
+    if B.dim() != 2 or B.shape[1] != n or B.shape[0] < 1:
+        raise ValueError(f"B must be [k >= 1, n={n}], got {tuple(B.shape)}")
+    diag_inv = _hip.check_tensor(diag_inv, "diag_inv", dtype=R.dtype, shape=(n,))
+    Z = torch.empty_like(R)
+    if Bt and n:
+        hd = _hip.get_handle(R.device)
+        hd.check(hd.lib.mgp_lowrank_apply(hd.h, _hip.dtype_code(R), _hip.ptr(diag_inv), _hip.ptr(B), B.shape[0], n,
+                                          _hip.ptr(R), Bt, _hip.ptr(Z)))
+    return Z
+
+
+def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e-16, check_every=10,
+                     preconditioner=None):
+    """CG from zero on `op` (a `conjugate_gradient.LinearOperator`) for the rows of rhs [Bt, n], no residual refresh,
+    recording every step taken (`mgp_pcg_solve_record`).  `preconditioner`: None (the identity) or a
+    `CGPreconditioner` whose native form libmgp records with (`EyePreconditioner`, `PivotedCholeskyPreconditioner`).
 
     Returns (solution [Bt, n], err [Bt, 1] = 0.5 rz, stats, coef [steps, Bt, 3] = (gamma, beta, 0.5 rz after the step))."""
     rhs = _hip.check_tensor(rhs, "rhs", dtype=op.dtype)
@@ -153,13 +197,19 @@ def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e
     if Bt > 0:
         hd = _hip.get_handle(op.device)
         st, keep = op._struct()
-        pre = _hip.MgpPrecond()
-        pre.kind = _hip.PRE_EYE
+        if preconditioner is None:
+            pre, pkeep = _hip.MgpPrecond(), ()
+            pre.kind = _hip.PRE_EYE
+        else:
+            nat = preconditioner._native(op)
+            if nat is None:
+                raise TypeError("the recording solve takes the identity or a preconditioner libmgp applies itself")
+            pre, pkeep = nat
         hd.check(hd.lib.mgp_pcg_solve_record(
             hd.h, ctypes.byref(st), ctypes.byref(pre), _hip.ptr(rhs), None, Bt, float(error_threshold), max_iterations,
             max_iterations + 1, float(min_float), int(check_every), _hip.ptr(sol), _hip.ptr(err), ctypes.byref(stats),
             _hip.ptr(coef), coef.shape[0]))
-        del keep
+        del keep, pkeep
     return sol, err, stats, coef[:stats.iterations]
 
 

@@ -11,6 +11,11 @@ Lanczos tridiagonal of the first m steps is (Golub & Van Loan 10.2; the mBCG sch
 and Gauss quadrature gives  z^T f(A) z  ~=  |z|^2 e1^T f(T) e1.  With Rademacher probes (E[z z^T] = I) the mean over
 probes of z^T log(A) z estimates log|A|.  T does not depend on the scale of z, so the solve may run on normalised
 columns and |z|^2 taken from the original probe.
+
+Preconditioned CG (preconditioner P, `MGP_PRE_LOWRANK`) is the same process on P^-1/2 A P^-1/2 started at P^-1/2 z:
+with gamma_k and beta_k = (r.z)_{k+1} / (r.z)_k of that solve the formulas above hold unchanged, the quadrature is
+z^T P^-1/2 f(P^-1/2 A P^-1/2) P^-1/2 z  ~=  (z^T P^-1 z) e1^T f(T) e1, and with probes drawn so that E[z z^T] = P the
+mean of the log-quadratures estimates log|A| - log|P|.  `norms2` is then the weight z^T P^-1 z of each column.
 """
 
 import numpy as np

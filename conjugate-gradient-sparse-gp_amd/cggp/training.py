@@ -214,17 +214,25 @@ class _GPRLmlEstimate(torch.autograd.Function):
 
     -- one `mgp_kxx_grad` call with u = 1/2 [alpha, -(P/t) W] and v = [alpha, Z]; the s2 term is the same form with
     dK = I, sum(u * v).  It is the Hutchinson estimate of the gradient (unbiased), not the exact derivative of the
-    fixed-probe value."""
+    fixed-probe value.
+
+    With a `PivotedCholeskyPreconditioner` P on `cg` the probes are draws from N(0, P) (`probes`, or
+    `P.sample(num_probes, seed=seed)` when `probes` is None) and the trace term is E[(Khat^-1 z)^T dK (P^-1 z)]:
+    v = [alpha, P^-1 Z].  P is held fixed within one evaluation (it is not differentiated); the estimator stays
+    unbiased because E[z z^T] = P whatever P is."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, s2, X, Y, probes, kind, cg):
+    def forward(ctx, variance, lengthscales, s2, X, Y, probes, kind, cg, num_probes=None, seed=0):
         from . import kernels
         from .models import GPR
         cls = {"se": kernels.SquaredExponential, "matern12": kernels.Matern12, "matern32": kernels.Matern32,
                "matern52": kernels.Matern52}[kind]
         kern = cls(variance=float(variance), lengthscales=[float(v) for v in lengthscales.reshape(-1)])
         model = GPR((X, Y), kern, noise_variance=float(s2), conjugate_gradient=cg, solver="cg")
-        est, alpha, W, Z = model._lml_estimate(probes=probes)
+        if probes is None:
+            est, alpha, W, Z = model._lml_estimate(num_probes=num_probes, seed=seed)
+        else:
+            est, alpha, W, Z = model._lml_estimate(probes=probes)
         P, t = Y.shape[1], Z.shape[1]
         U = 0.5 * torch.cat([alpha, -(float(P) / t) * W], dim=1).contiguous()
         V = torch.cat([alpha, Z], dim=1).contiguous()
@@ -241,7 +249,7 @@ class _GPRLmlEstimate(torch.autograd.Function):
         n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
         gl = torch.tensor(dls if n_l > 1 else [sum(dls)], dtype=torch.float64).reshape(ctx.l_shape)
         return (g * torch.tensor(dvar, dtype=torch.float64), g * gl, g * torch.tensor(ds2, dtype=torch.float64),
-                None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
 class TrainableGPR:
@@ -254,7 +262,10 @@ class TrainableGPR:
     `num_probes=t`: matrix-free at any N.  The value is `GPR.log_marginal_likelihood_estimate` with t Rademacher
     probes (drawn once from `probe_seed`, fixed per model so repeated evaluations at one theta agree; `resample_probes`
     draws new ones), solved by `conjugate_gradient` (default `ConjugateGradient(1e-8)`, from zero: Lanczos needs
-    x0 = 0, so there is no warm start).  The gradient comes from one `mgp_kxx_grad` call (`_GPRLmlEstimate`).  It is
+    x0 = 0, so there is no warm start).  With `ConjugateGradient(thr, preconditioner=PivotedCholeskyPreconditioner())`
+    the solve is preconditioned and the probes are draws from N(0, P) re-formed from the current factor and the normals
+    of `probe_seed`; a probe set assigned to `self.probes` by the caller is then taken as draws with E[z z^T] = P.
+    The gradient comes from one `mgp_kxx_grad` call (`_GPRLmlEstimate`).  It is
     an unbiased estimate of the true gradient, NOT the exact derivative of the fixed-probe value, so an L-BFGS line
     search may see the two disagree: Adam is the tested optimiser here."""
 
@@ -267,7 +278,7 @@ class TrainableGPR:
             raise ValueError("num_probes must be None or >= 1")
         self.probe_seed = int(probe_seed)
         self.conjugate_gradient = conjugate_gradient or ConjugateGradient(1e-8)
-        self.probes = None
+        self.probes = self._drawn_probes = None
         if self.num_probes is not None:
             self.resample_probes(self.probe_seed)
 
@@ -278,16 +289,31 @@ class TrainableGPR:
         self.probe_seed = self.probe_seed + 1 if seed is None else int(seed)
         gen = torch.Generator().manual_seed(self.probe_seed)
         z = torch.randint(0, 2, (self.X.shape[0], self.num_probes), generator=gen, dtype=torch.int64) * 2 - 1
-        self.probes = z.to(device=self.X.device, dtype=self.X.dtype)
+        self.probes = self._drawn_probes = z.to(device=self.X.device, dtype=self.X.dtype)
         return self.probes
 
     def parameters(self):
         return self.kernel.parameters() + [self.likelihood_variance.raw]
 
+    def _sampled_probes(self):
+        """True when the CG carries a `PivotedCholeskyPreconditioner` and no explicit probe set was installed
+        (`self.probes` replaced by the caller): the probes are then sampled from N(0, P)."""
+        from .conjugate_gradient import PivotedCholeskyPreconditioner
+        return (isinstance(self.conjugate_gradient.preconditioner, PivotedCholeskyPreconditioner)
+                and self.probes is self._drawn_probes)
+
     def log_marginal_likelihood(self, data=None):
         X, Y = (self.X, self.Y) if data is None else data
         N, P = Y.shape
         s2 = self.likelihood_variance()
+        if self.num_probes is not None and self._sampled_probes():
+            # probes from N(0, P): g1, g2 are drawn once per probe_seed and Z = L^T g1 + sigma g2 is re-formed from
+            # the factor of the current theta, so repeated evaluations at one theta agree
+            ls = self.kernel.lengthscales_p()
+            if ls.dim() == 0:
+                ls = ls.reshape(1)
+            return _GPRLmlEstimate.apply(self.kernel.variance_p(), ls, s2, X.contiguous(), Y.contiguous(), None,
+                                         self.kernel.name, self.conjugate_gradient, self.num_probes, self.probe_seed)
         if self.num_probes is not None:
             probes = self.probes if self.probes.shape[0] == N else None
             if probes is None:  # another row count than the model's own data: a draw of that size

@@ -135,6 +135,9 @@ __global__ __launch_bounds__(NTB) void cg_update_kernel(const CgCtrl* __restrict
       v[off + j] = mgp_fma(gamma, p[off + j], v[off + j]);
       if (mode != 1) r[off + j] = mgp_fma(-gamma, ap[off + j], r[off + j]);
     }
+    // recording solve on the split-update route: the step length is known here, beta and rz in mode 4
+    if (mode == 3 && coef != nullptr && threadIdx.x == 0 && ctrl->iters < coef_steps)
+      coef[((long)ctrl->iters * gridDim.x + blockIdx.x) * 3] = gamma;
     if (mode != 0) return;
     __syncthreads();
   }
@@ -159,10 +162,10 @@ __global__ __launch_bounds__(NTB) void cg_update_kernel(const CgCtrl* __restrict
   const bool drop = mode == 2 || mode == 5 || rz_old <= min_float;
   for (long j = threadIdx.x; j < n; j += blockDim.x) p[off + j] = drop ? zz[j] : mgp_fma(beta, p[off + j], zz[j]);
   if (threadIdx.x == 0) {
-    // recording solve (mode 0 only; the step index is the counter cg_advance_kernel moves after this launch)
-    if (coef != nullptr && mode == 0 && ctrl->iters < coef_steps) {
+    // recording solve (modes 0 and 4; the step index is the counter cg_advance_kernel moves after this launch)
+    if (coef != nullptr && (mode == 0 || mode == 4) && ctrl->iters < coef_steps) {
       T* c = coef + ((long)ctrl->iters * gridDim.x + blockIdx.x) * 3;
-      c[0] = gamma;
+      if (mode == 0) c[0] = gamma;
       c[1] = beta;
       c[2] = (T)0.5 * s_rz;
     }
@@ -565,6 +568,7 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
   PrecondDev pc{MGP_PRE_EYE, 0, 0, nullptr, nullptr, nullptr};
   const void* dense_inv = nullptr;  // MGP_PRE_DENSE: z = r @ Pinv through the symmetric product kernels
   const mgp_precond* cb = nullptr;  // MGP_PRE_CALLBACK: z produced by the caller's function, same step structure
+  const mgp_precond* lowrank = nullptr;  // MGP_PRE_LOWRANK: z = diag_inv o r - (r B^T) B (pivchol.hip)
   if (pre) {
     pc.kind = pre->kind;
     if (pre->kind == MGP_PRE_JACOBI) {
@@ -584,11 +588,15 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
       if (!pre->apply || !pre->cb_r || !pre->cb_z)
         return mgp_fail(h, MGP_E_BADARG, "callback preconditioner needs apply, cb_r and cb_z");
       cb = pre;
+    } else if (pre->kind == MGP_PRE_LOWRANK) {
+      if (!pre->diag_inv || !pre->dense_inv || pre->num_blocks < 1)
+        return mgp_fail(h, MGP_E_BADARG, "low-rank preconditioner needs diag_inv, B (dense_inv) and k (num_blocks) >= 1");
+      lowrank = pre;
     } else if (pre->kind != MGP_PRE_EYE) {
       return mgp_fail(h, MGP_E_BADARG, "unknown preconditioner kind %d", pre->kind);
     }
   }
-  const bool dense_pre = dense_inv != nullptr || cb != nullptr;  // z comes from outside the update kernels
+  const bool dense_pre = dense_inv != nullptr || cb != nullptr || lowrank != nullptr;  // z comes from outside the update kernels
   const bool need_z = pc.kind != MGP_PRE_EYE && cb == nullptr;   // dense: z = r @ Pinv lives in the arena
   if (dense_pre) pc.kind = MGP_PRE_EYE;                          // the update kernels never apply it themselves
   // arena: r, p, ap, [z], rz[Bt], over[Bt] (int), ctrl
@@ -631,6 +639,9 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
       if (rc != 0) return mgp_fail(h, MGP_E_BADARG, "preconditioner callback returned %d", rc);
       return MGP_OK;
     }
+    if (lowrank)
+      return mgp_lowrank_apply_gated(h, op->dtype, lowrank->diag_inv, lowrank->dense_inv, lowrank->num_blocks, n, r, Bt,
+                                     z, gate);
     return mgp_symm_matmul_gated(h, op->dtype, dense_inv, n, r, Bt, z, gate);
   };
 
@@ -790,11 +801,11 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
                              over, err_out, n, (T)thr, (T)min_float, pc, 0, 0, coef, coef_steps);
         } else {
           MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 3, 0, (T*)nullptr, 0L);
+                             over, err_out, n, (T)thr, (T)min_float, pc, 3, 0, coef, coef_steps);
           MGP_LAUNCH_CHECK(h);
           MGP_TRY(external_z(&ctrl->active));
           MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 4, 0, (T*)nullptr, 0L);
+                             over, err_out, n, (T)thr, (T)min_float, pc, 4, 0, coef, coef_steps);
         }
       } else {
         MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
@@ -890,15 +901,16 @@ extern "C" int mgp_pcg_solve(mgp_handle* h, const mgp_operator* op, const mgp_pr
                          check_every, V_out, err_out, stats, nullptr, 0);
 }
 
-// Recording solve (stochastic Lanczos quadrature): the Eye-preconditioned update kernels write (gamma, beta, 0.5 rz)
-// of every step taken into coef[step, b]; the register-resident dense route is not taken (pcg_solve_t).
+// Recording solve (stochastic Lanczos quadrature): the update kernels write (gamma, beta, 0.5 rz) of every step taken
+// into coef[step, b] -- the fused and mode-0 kernels with the identity, the split update (modes 3 and 4) with
+// MGP_PRE_LOWRANK; the register-resident dense route is not taken (pcg_solve_t).
 extern "C" int mgp_pcg_solve_record(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B,
                                     const void* V0, int64_t Bt, double error_threshold, int64_t max_iterations,
                                     int64_t max_steps_cycle, double min_float, int32_t check_every, void* V_out,
                                     void* err_out, mgp_cg_stats* stats, void* coef, int64_t coef_steps) {
   if (!h) return MGP_E_BADARG;
-  if (pre != nullptr && pre->kind != MGP_PRE_EYE)
-    return mgp_fail(h, MGP_E_BADARG, "recording solve: only the identity preconditioner (MGP_PRE_EYE)");
+  if (pre != nullptr && pre->kind != MGP_PRE_EYE && pre->kind != MGP_PRE_LOWRANK)
+    return mgp_fail(h, MGP_E_BADARG, "recording solve: only the identity (MGP_PRE_EYE) and MGP_PRE_LOWRANK preconditioners");
   if (coef == nullptr) return mgp_fail(h, MGP_E_BADARG, "recording solve: coef is NULL");
   if (coef_steps < 0) return mgp_fail(h, MGP_E_BADARG, "recording solve: coef_steps < 0");
   return pcg_solve_entry(h, op, pre, B, V0, Bt, error_threshold, max_iterations, max_steps_cycle, min_float,

@@ -37,6 +37,10 @@ struct mgp_handle {
   size_t kgrad_bytes = 0;
   int kxx_grad_mode = 0;  // mgp_kxx_grad: 0 = fused pair kernel where it serves (fp64, D <= 32; MGP_KXX_GRAD=fused),
                           // 2 = row panels through mgp_k_dense_vjp everywhere (MGP_KXX_GRAD=panel)
+  // pivoted Cholesky of k(X,X) and the low-rank preconditioner application (pivchol.hip): the residual diagonal and
+  // the step partials of a build, or the column-chunk partials of r B^T
+  void* pch = nullptr;
+  size_t pch_bytes = 0;
   // generic-D scratch (transposed multipliers, kernel panel, chunk output)
   void* gen = nullptr;
   size_t gen_bytes = 0;
@@ -378,3 +382,6 @@ int mgp_symm_gemv_rows_acc(mgp_handle* h, int dtype, const void* A, int64_t n, c
 int mgp_comm_allreduce_on(mgp_handle* h, mgp_comm* comm, void* buf, size_t count, int dtype);
 int mgp_symm_matmul_gated(mgp_handle* h, int dtype, const void* A, int64_t n, const void* P, int64_t Bt,
                           void* out, const int* gate);
+// pivchol.hip: Z[Bt, n] = diag_inv o R - (R B^T) B, B [k, n]; gate: device int, skip if 0
+int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
+                            const void* R, int64_t Bt, void* Z, const int* gate);

@@ -1,0 +1,399 @@
+// pivchol.hip -- matrix-free partial pivoted Cholesky of k(X, X) and the diagonal-plus-low-rank preconditioner
+// application built on it (Harbrecht, Peters & Schneider 2012; Gardner et al. 2018, the mBCG preconditioner).
+//
+// mgp_kxx_pivchol: greedy rank-k factor K ~= L^T L, L [k, N] row-major.  Step i needs the pivot p_i = argmax d, the
+// row k(x_p, X) and the i earlier rows of L -- 8 i N bytes streamed once, the whole build about 4 k^2 N bytes.  One
+// launch per step, no host round trip: every workgroup of step i first reduces the (max, index, sum) partials that
+// the workgroups of step i - 1 left (double-buffered), so all of them know p_i, then forms its own slice of row i,
+// updates its slice of d and leaves its own partial for step i + 1.  The argmax (lowest index on ties) and the
+// trace are reduced in a fixed order: two calls give the same bits.  No spin waits between workgroups, no
+// persistent grid.
+//
+// mgp_lowrank_apply: z = dinv o r - (r B^T) B for row batches, B [k, n].  Pass 1 is a reduction over n in two
+// stages (column-chunk partials, then their sum in chunk order; no float atomics), pass 2 forms z.  Both stream B
+// once; they are bandwidth-bound.  The gated form is the MGP_PRE_LOWRANK step of the device CG loop (cg.hip).
+#include "mgp_common.h"
+
+namespace {
+
+constexpr int PC_NT = 256;        // threads per workgroup of the factor kernels
+constexpr int PC_MAX_WG = 512;    // workgroups per step (each reads every partial of the step before)
+constexpr int PC_MAX_RANK = 1024;
+
+struct PcState {
+  int rank;     // rows of L written so far that count (set when the build stops early)
+  int stopped;  // a step found the trace under the tolerance or no positive pivot
+};
+
+// (max, lowest index of the max, sum) of the workgroup's values; every thread returns the same triple
+struct PcTriple {
+  double mx;
+  long ix;
+  double sm;
+};
+
+__device__ __forceinline__ void pc_take(PcTriple& a, double mx, long ix) {
+  if (mx > a.mx || (mx == a.mx && ix < a.ix)) {
+    a.mx = mx;
+    a.ix = ix;
+  }
+}
+
+__device__ __forceinline__ PcTriple pc_block_reduce(PcTriple v, double* smx, long* six, double* ssm) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const double omx = __shfl_xor(v.mx, off, 64);
+    const long oix = __shfl_xor(v.ix, off, 64);
+    v.sm += __shfl_xor(v.sm, off, 64);
+    pc_take(v, omx, oix);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();  // the LDS slots may still be read from the previous reduction
+  if (lane == 0) {
+    smx[wave] = v.mx;
+    six[wave] = v.ix;
+    ssm[wave] = v.sm;
+  }
+  __syncthreads();
+  PcTriple r{smx[0], six[0], ssm[0]};
+  for (int w = 1; w < PC_NT / 64; ++w) {  // fixed order
+    pc_take(r, smx[w], six[w]);
+    r.sm += ssm[w];
+  }
+  return r;
+}
+
+// k(x_p, x_c) / variance from direct differences of the rows scaled by 1 / lengthscale (the forms of grad.hip:
+// GPflow's K_r2 / K_r with its 1e-36 floor under the square root)
+template <int KIND>
+__device__ __forceinline__ double pc_profile(double r2) {
+  if (KIND == 0) return mgp_exp2(-0.5 * MGP_LOG2E * r2);
+  const double r = mgp_sqrt(r2 > 1e-36 ? r2 : 1e-36);
+  if (KIND == 1) return mgp_exp2(-MGP_LOG2E * r);
+  if (KIND == 2) {
+    const double s3 = 1.7320508075688772935;
+    return (1.0 + s3 * r) * mgp_exp2(-MGP_LOG2E * s3 * r);
+  }
+  const double s5 = 2.2360679774997896964;
+  return (1.0 + s5 * r + (5.0 / 3.0) * r2) * mgp_exp2(-MGP_LOG2E * s5 * r);
+}
+
+// d = variance everywhere, the partials of step 0, the state word
+__global__ __launch_bounds__(PC_NT) void pivchol_init_kernel(double* __restrict__ d, long N, long slice, double variance,
+                                                              double* __restrict__ pmx, long* __restrict__ pix,
+                                                              double* __restrict__ psm, PcState* __restrict__ st,
+                                                              int max_rank) {
+  __shared__ double smx[PC_NT / 64], ssm[PC_NT / 64];
+  __shared__ long six[PC_NT / 64];
+  const long c0 = (long)blockIdx.x * slice;
+  const long c1 = c0 + slice < N ? c0 + slice : N;
+  PcTriple v{-1.0, N, 0.0};
+  for (long c = c0 + threadIdx.x; c < c1; c += PC_NT) {
+    d[c] = variance;
+    pc_take(v, variance, c);
+    v.sm += variance;
+  }
+  v = pc_block_reduce(v, smx, six, ssm);
+  if (threadIdx.x == 0) {
+    pmx[blockIdx.x] = v.mx;
+    pix[blockIdx.x] = v.ix;
+    psm[blockIdx.x] = v.sm;
+    if (blockIdx.x == 0) {
+      st->rank = max_rank;
+      st->stopped = 0;
+    }
+  }
+}
+
+// Step i of the factor.  `in` partials come from step i - 1 (or the init kernel), `out` go to step i + 1.
+template <int KIND>
+__global__ __launch_bounds__(PC_NT) void pivchol_step_kernel(const double* __restrict__ X, long N, int D,
+                                                              const double* __restrict__ inv_ls, double variance,
+                                                              double stop_sum, int i, double* __restrict__ L,
+                                                              double* __restrict__ d, long* __restrict__ piv, long slice,
+                                                              const double* __restrict__ in_mx, const long* __restrict__ in_ix,
+                                                              const double* __restrict__ in_sm, double* __restrict__ out_mx,
+                                                              long* __restrict__ out_ix, double* __restrict__ out_sm,
+                                                              PcState* __restrict__ st) {
+  if (st->stopped) return;  // written by an earlier launch
+  __shared__ double smx[PC_NT / 64], ssm[PC_NT / 64];
+  __shared__ long six[PC_NT / 64];
+  __shared__ double xp[MGP_MAX_D];   // the pivot's row, scaled
+  __shared__ double sinv[MGP_MAX_D];
+  __shared__ double lp[PC_MAX_RANK];  // L[j, p] for j < i
+  const int t = threadIdx.x;
+  // every workgroup reduces all partials of the step before, in the same order: the same pivot and trace everywhere
+  PcTriple g{-1.0, N, 0.0};
+  for (int w = t; w < (int)gridDim.x; w += PC_NT) {
+    pc_take(g, in_mx[w], in_ix[w]);
+    g.sm += in_sm[w];
+  }
+  g = pc_block_reduce(g, smx, six, ssm);
+  if (!(g.sm > stop_sum) || !(g.mx > 0.0)) {
+    if (blockIdx.x == 0 && t == 0) {
+      st->rank = i;
+      st->stopped = 1;
+    }
+    return;
+  }
+  const long p = g.ix;
+  const double inv_root = 1.0 / mgp_sqrt(g.mx);
+  for (int e = t; e < D; e += PC_NT) {
+    const double s = inv_ls[e];
+    sinv[e] = s;
+    xp[e] = X[p * D + e] * s;
+  }
+  for (int j = t; j < i; j += PC_NT) lp[j] = L[(long)j * N + p];
+  if (blockIdx.x == 0 && t == 0) piv[i] = p;
+  __syncthreads();
+  const long c0 = (long)blockIdx.x * slice;
+  const long c1 = c0 + slice < N ? c0 + slice : N;
+  double* __restrict__ Li = L + (long)i * N;
+  PcTriple v{-1.0, N, 0.0};
+  for (long c = c0 + t; c < c1; c += PC_NT) {
+    const double dc = d[c];
+    double lv = 0.0, dn = 0.0;
+    // a column whose residual diagonal is exactly 0 -- every earlier pivot, and the pivot itself below -- keeps an
+    // exact 0 in this row: its residual row is 0 in exact arithmetic (K is positive semi-definite)
+    if (c == p) {
+      lv = g.mx * inv_root;  // sqrt(d_p)
+    } else if (dc > 0.0) {
+      double r2 = 0.0;
+      const double* __restrict__ xc = X + c * D;
+      for (int e = 0; e < D; ++e) {
+        const double df = xc[e] * sinv[e] - xp[e];
+        r2 = mgp_fma(df, df, r2);
+      }
+      double acc = variance * pc_profile<KIND>(r2);
+#pragma unroll 8
+      for (int j = 0; j < i; ++j) acc = mgp_fma(-lp[j], L[(long)j * N + c], acc);
+      lv = acc * inv_root;
+      dn = mgp_fma(-lv, lv, dc);
+      dn = dn > 0.0 ? dn : 0.0;
+    }
+    Li[c] = lv;
+    d[c] = dn;
+    pc_take(v, dn, c);
+    v.sm += dn;
+  }
+  v = pc_block_reduce(v, smx, six, ssm);
+  if (t == 0) {
+    out_mx[blockIdx.x] = v.mx;
+    out_ix[blockIdx.x] = v.ix;
+    out_sm[blockIdx.x] = v.sm;
+  }
+}
+
+// ---- z = dinv o r - (r B^T) B ------------------------------------------------------------------------------------
+constexpr int LR_ROWS = 16;      // rows of B per workgroup of pass 1 (four per wavefront)
+constexpr int LR_LDS_ELEMS = 2048;  // elements of r a workgroup of pass 1 stages (chunk columns x columns of the batch)
+constexpr int LR_TILE = 128;     // rows of B whose coefficients pass 2 stages at a time
+
+// pass 1: part[chunk, b, i] = sum over the chunk's columns j of R[b, j] B[i, j]
+template <typename T, int BT>
+__global__ __launch_bounds__(256) void lowrank_dot_kernel(const int* __restrict__ gate, const T* __restrict__ B, long k,
+                                                          long n, const T* __restrict__ R, int bt, long chunk,
+                                                          T* __restrict__ part) {
+  if (gate != nullptr && *gate == 0) return;
+  __shared__ T rs[LR_LDS_ELEMS];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const long c0 = (long)blockIdx.x * chunk;
+  const long cn = (c0 + chunk < n ? c0 + chunk : n) - c0;  // columns of this chunk
+  for (long e = t; e < (long)BT * chunk; e += 256) {
+    const long b = e / chunk, j = e - b * chunk;
+    rs[e] = (b < bt && j < cn) ? R[b * n + c0 + j] : (T)0;
+  }
+  __syncthreads();
+  const long i0 = (long)blockIdx.y * LR_ROWS;
+  for (int q = wave; q < LR_ROWS; q += 4) {
+    const long i = i0 + q;
+    if (i >= k) break;  // wave-uniform
+    const T* __restrict__ Bi = B + i * n + c0;
+    T acc[BT];
+#pragma unroll
+    for (int b = 0; b < BT; ++b) acc[b] = 0;
+    for (long j = lane; j < cn; j += 64) {
+      const T bv = Bi[j];
+#pragma unroll
+      for (int b = 0; b < BT; ++b) acc[b] = mgp_fma(bv, rs[b * chunk + j], acc[b]);
+    }
+#pragma unroll
+    for (int b = 0; b < BT; ++b) {
+      T v = acc[b];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0 && b < bt) part[((long)blockIdx.x * bt + b) * k + i] = v;
+    }
+  }
+}
+
+// stage 2 of pass 1: tt[b, i] = sum over chunks, in chunk order
+template <typename T>
+__global__ __launch_bounds__(256) void lowrank_sum_kernel(const int* __restrict__ gate, const T* __restrict__ part,
+                                                          long nchunks, long total, T* __restrict__ tt) {
+  if (gate != nullptr && *gate == 0) return;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  T s = 0;
+  for (long c = 0; c < nchunks; ++c) s += part[c * total + e];
+  tt[e] = s;
+}
+
+// pass 2: Z[b, j] = dinv[j] R[b, j] - sum_i tt[b, i] B[i, j]
+template <typename T, int BT>
+__global__ __launch_bounds__(256) void lowrank_form_kernel(const int* __restrict__ gate, const T* __restrict__ dinv,
+                                                           const T* __restrict__ B, long k, long n,
+                                                           const T* __restrict__ R, int bt, const T* __restrict__ tt,
+                                                           T* __restrict__ Z) {
+  if (gate != nullptr && *gate == 0) return;
+  __shared__ T ts[BT * LR_TILE];
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  const long jc = j < n ? j : n - 1;
+  T acc[BT];
+#pragma unroll
+  for (int b = 0; b < BT; ++b) acc[b] = 0;
+  for (long i0 = 0; i0 < k; i0 += LR_TILE) {
+    const int lim = (int)(k - i0 < LR_TILE ? k - i0 : LR_TILE);
+    __syncthreads();
+    for (int e = threadIdx.x; e < BT * LR_TILE; e += 256) {
+      const int b = e / LR_TILE, q = e - b * LR_TILE;
+      ts[e] = (b < bt && q < lim) ? tt[(long)b * k + i0 + q] : (T)0;
+    }
+    __syncthreads();
+    const T* __restrict__ Bc = B + i0 * n + jc;
+#pragma unroll 8
+    for (int q = 0; q < lim; ++q) {
+      const T bv = Bc[(long)q * n];
+#pragma unroll
+      for (int b = 0; b < BT; ++b) acc[b] = mgp_fma(ts[b * LR_TILE + q], bv, acc[b]);
+    }
+  }
+  if (j >= n) return;
+  const T dv = dinv[j];
+#pragma unroll
+  for (int b = 0; b < BT; ++b)
+    if (b < bt) Z[(long)b * n + j] = mgp_fma(dv, R[(long)b * n + j], -acc[b]);
+}
+
+// columns of a pass-1 chunk for a batch rounded up to BT columns: a multiple of 64, at most 2048
+inline long lr_chunk(int BT) { return LR_LDS_ELEMS / BT; }
+
+template <typename T, int BT>
+int lowrank_group(mgp_handle* h, const T* dinv, const T* B, long k, long n, const T* R, int bt, T* Z, const int* gate) {
+  const long chunk = lr_chunk(BT);
+  const long nchunks = (n + chunk - 1) / chunk;
+  const long total = (long)bt * k;
+  MGP_TRY(mgp_reserve(h, &h->pch, &h->pch_bytes, (size_t)(nchunks + 1) * total * sizeof(T)));
+  T* part = (T*)h->pch;
+  T* tt = part + nchunks * total;
+  hipLaunchKernelGGL((lowrank_dot_kernel<T, BT>), dim3((unsigned)nchunks, (unsigned)((k + LR_ROWS - 1) / LR_ROWS)),
+                     dim3(256), 0, h->stream, gate, B, k, n, R, bt, chunk, part);
+  MGP_LAUNCH_CHECK(h);
+  hipLaunchKernelGGL((lowrank_sum_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, gate,
+                     (const T*)part, nchunks, total, tt);
+  MGP_LAUNCH_CHECK(h);
+  hipLaunchKernelGGL((lowrank_form_kernel<T, BT>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, gate,
+                     dinv, B, k, n, R, bt, (const T*)tt, Z);
+  MGP_LAUNCH_CHECK(h);
+  return MGP_OK;
+}
+
+template <typename T>
+int lowrank_apply_t(mgp_handle* h, const T* dinv, const T* B, long k, long n, const T* R, long Bt, T* Z,
+                    const int* gate) {
+  // batches of more than 16 rows go in groups of 16 (B is read once per group)
+  for (long b0 = 0; b0 < Bt; b0 += 16) {
+    const int bt = (int)(Bt - b0 < 16 ? Bt - b0 : 16);
+    const T* Rg = R + b0 * n;
+    T* Zg = Z + b0 * n;
+    if (bt == 1) MGP_TRY((lowrank_group<T, 1>(h, dinv, B, k, n, Rg, bt, Zg, gate)));
+    else if (bt == 2) MGP_TRY((lowrank_group<T, 2>(h, dinv, B, k, n, Rg, bt, Zg, gate)));
+    else if (bt <= 4) MGP_TRY((lowrank_group<T, 4>(h, dinv, B, k, n, Rg, bt, Zg, gate)));
+    else if (bt <= 8) MGP_TRY((lowrank_group<T, 8>(h, dinv, B, k, n, Rg, bt, Zg, gate)));
+    else MGP_TRY((lowrank_group<T, 16>(h, dinv, B, k, n, Rg, bt, Zg, gate)));
+  }
+  return MGP_OK;
+}
+
+}  // namespace
+
+// internal: the gated form the CG loop enqueues (steps past convergence do nothing)
+int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
+                            const void* R, int64_t Bt, void* Z, const int* gate) {
+  if (dtype == MGP_F64)
+    return lowrank_apply_t<double>(h, (const double*)diag_inv, (const double*)B, k, n, (const double*)R, Bt, (double*)Z,
+                                   gate);
+  return lowrank_apply_t<float>(h, (const float*)diag_inv, (const float*)B, k, n, (const float*)R, Bt, (float*)Z, gate);
+}
+
+extern "C" int mgp_lowrank_apply(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
+                                 const void* R, int64_t Bt, void* Z) {
+  if (!h) return MGP_E_BADARG;
+  if (dtype != MGP_F32 && dtype != MGP_F64) return mgp_fail(h, MGP_E_DTYPE, "bad dtype %d", dtype);
+  if (k < 1 || n < 0 || Bt < 0) return mgp_fail(h, MGP_E_SHAPE, "low-rank apply needs k >= 1, n >= 0, Bt >= 0");
+  if (n == 0 || Bt == 0) return MGP_OK;
+  if (!diag_inv || !B || !R || !Z) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
+  if (R == Z) return mgp_fail(h, MGP_E_BADARG, "low-rank apply is not in place (R == Z)");
+  return mgp_lowrank_apply_gated(h, dtype, diag_inv, B, k, n, R, Bt, Z, nullptr);
+}
+
+extern "C" int mgp_kxx_pivchol(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, int32_t max_rank,
+                               double rel_tol, void* L, int64_t* piv, void* diag, int32_t* rank_out) {
+  if (!h) return MGP_E_BADARG;
+  MGP_TRY(mgp_check_kernel(h, k));
+  if (k->dtype != MGP_F64) return mgp_fail(h, MGP_E_DTYPE, "the pivoted Cholesky factor is fp64 only");
+  if (N < 0) return mgp_fail(h, MGP_E_SHAPE, "N < 0");
+  if (max_rank < 1 || max_rank > PC_MAX_RANK)
+    return mgp_fail(h, MGP_E_BADARG, "max_rank=%d outside [1, %d]", max_rank, PC_MAX_RANK);
+  if (!(rel_tol >= 0.0)) return mgp_fail(h, MGP_E_BADARG, "rel_tol must be >= 0");
+  if (!rank_out) return mgp_fail(h, MGP_E_BADARG, "rank_out is NULL");
+  *rank_out = 0;
+  if (N == 0) return MGP_OK;
+  if (!X || !L || !piv) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
+  const int kmax = (int64_t)max_rank > N ? (int)N : max_rank;
+  // workgroups: slices of a multiple of 256 columns, at most PC_MAX_WG of them
+  long slice = (N + PC_MAX_WG - 1) / PC_MAX_WG;
+  slice = (slice + PC_NT - 1) / PC_NT * PC_NT;
+  const long G = (N + slice - 1) / slice;
+  // arena: d [N] | partials 2 x (max, index, sum) [G] | 1/lengthscale [D] | state
+  const size_t nd = ((size_t)N + 31) & ~(size_t)31;
+  const size_t need = (nd + 6 * (size_t)PC_MAX_WG + MGP_MAX_D) * sizeof(double) + 256;
+  MGP_TRY(mgp_reserve(h, &h->pch, &h->pch_bytes, need));
+  double* d = (double*)h->pch;
+  double* pmx[2] = {d + nd, d + nd + PC_MAX_WG};
+  double* psm[2] = {d + nd + 2 * PC_MAX_WG, d + nd + 3 * PC_MAX_WG};
+  long* pix[2] = {(long*)(d + nd + 4 * PC_MAX_WG), (long*)(d + nd + 5 * PC_MAX_WG)};
+  double* inv_ls = d + nd + 6 * PC_MAX_WG;
+  PcState* st = (PcState*)(inv_ls + MGP_MAX_D);
+  hipStream_t s = h->stream;
+  double host_inv[MGP_MAX_D];
+  for (int e = 0; e < k->D; ++e) host_inv[e] = 1.0 / k->lengthscales[e];
+  MGP_HIP(h, hipMemcpyAsync(inv_ls, host_inv, (size_t)k->D * sizeof(double), hipMemcpyHostToDevice, s));
+  MGP_HIP(h, hipStreamSynchronize(s));  // host_inv is a stack temporary
+  hipLaunchKernelGGL(pivchol_init_kernel, dim3((unsigned)G), dim3(PC_NT), 0, s, d, (long)N, slice, k->variance, pmx[0],
+                     pix[0], psm[0], st, kmax);
+  MGP_LAUNCH_CHECK(h);
+  const double stop_sum = rel_tol * (double)N * k->variance;
+  for (int i = 0; i < kmax; ++i) {
+    const int a = i & 1, b = a ^ 1;
+#define MGP_PC(KV)                                                                                                   \
+  hipLaunchKernelGGL((pivchol_step_kernel<KV>), dim3((unsigned)G), dim3(PC_NT), 0, s, (const double*)X, (long)N, k->D, \
+                     (const double*)inv_ls, k->variance, stop_sum, i, (double*)L, d, (long*)piv, slice,                \
+                     (const double*)pmx[a], (const long*)pix[a], (const double*)psm[a], pmx[b], pix[b], psm[b], st)
+    switch (k->kind) {
+      case MGP_SE: MGP_PC(0); break;
+      case MGP_MATERN12: MGP_PC(1); break;
+      case MGP_MATERN32: MGP_PC(2); break;
+      default: MGP_PC(3); break;
+    }
+#undef MGP_PC
+    MGP_LAUNCH_CHECK(h);
+  }
+  if (diag) MGP_HIP(h, hipMemcpyAsync(diag, d, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));
+  PcState host_st{0, 0};
+  MGP_HIP(h, hipMemcpyAsync(h->host_flag, st, sizeof(PcState), hipMemcpyDeviceToHost, s));
+  MGP_HIP(h, hipStreamSynchronize(s));
+  memcpy(&host_st, h->host_flag, sizeof(PcState));
+  *rank_out = host_st.rank;
+  return MGP_OK;
+}

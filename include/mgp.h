@@ -52,7 +52,12 @@ enum { MGP_SE = 0, MGP_MATERN12 = 1, MGP_MATERN32 = 2, MGP_MATERN52 = 3 };
  * function-level layout of conjugate_gradient(), conjugate_gradient.py:24-32). */
 enum { MGP_COLS = 0, MGP_ROWS = 1 };
 
-enum { MGP_PRE_EYE = 0, MGP_PRE_JACOBI = 1, MGP_PRE_BLOCK = 2, MGP_PRE_DENSE = 3, MGP_PRE_CALLBACK = 4 };
+/* MGP_PRE_LOWRANK: diagonal plus low rank, z = diag_inv o r - (r B^T) B for each row of the batch, applied inside the
+ * device CG loop (mgp_lowrank_apply's kernels, gated).  It reuses three fields of mgp_precond: diag_inv = D^-1 [n],
+ * dense_inv = B [k, n] row-major, num_blocks = k >= 1.  For P = D + L^T L (L [k, n], e.g. mgp_kxx_pivchol's factor and
+ * D = s2 I) pass B = C^-1 L D^-1 with C C^T = I_k + L D^-1 L^T (Woodbury); P^-1 must be positive definite. */
+enum { MGP_PRE_EYE = 0, MGP_PRE_JACOBI = 1, MGP_PRE_BLOCK = 2, MGP_PRE_DENSE = 3, MGP_PRE_CALLBACK = 4,
+       MGP_PRE_LOWRANK = 5 };
 
 /* MGP_OP_KXX_NOISE: (k(X,X) + s2 I) applied matrix-free with each unordered pair evaluated once (mgp_kxx_matvec);
  * fields kernel, X, N, s2 and n == N; single rank: `allreduce` / `comm` set is MGP_E_BADARG */
@@ -128,11 +133,11 @@ typedef int (*mgp_precond_fn)(void* ctx, const void* r, void* z, int64_t Bt, int
 typedef struct {
   int32_t kind;               /* MGP_PRE_* */
   int32_t block_size;         /* MGP_PRE_BLOCK: bs */
-  int64_t num_blocks;         /* MGP_PRE_BLOCK: nb */
-  const void* diag_inv;       /* MGP_PRE_JACOBI: 1/diag(A) [n] device */
+  int64_t num_blocks;         /* MGP_PRE_BLOCK: nb; MGP_PRE_LOWRANK: k, the rows of B */
+  const void* diag_inv;       /* MGP_PRE_JACOBI: 1/diag(A) [n] device; MGP_PRE_LOWRANK: D^-1 [n] device */
   const int64_t* block_index; /* MGP_PRE_BLOCK: [nb, bs] int64 device */
   const void* block_inv;      /* MGP_PRE_BLOCK: inverse of A[idx,idx], [nb, bs, bs] device */
-  const void* dense_inv;      /* MGP_PRE_DENSE: symmetric P^-1 [n, n] device; z = r @ P^-1 */
+  const void* dense_inv;      /* MGP_PRE_DENSE: symmetric P^-1 [n, n] device; z = r @ P^-1; MGP_PRE_LOWRANK: B [k, n] device */
   mgp_precond_fn apply;       /* MGP_PRE_CALLBACK */
   void* apply_ctx;
   void* cb_r;                 /* MGP_PRE_CALLBACK: [Bt, n] device, receives r before every call */
@@ -201,6 +206,29 @@ int mgp_kmn_sq_colsum(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t
  * or 32 -- O(N), nothing N x N (N = 2^20, D = 32, R = 8: 904 MiB). */
 int mgp_kxx_matvec(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, const void* V, int32_t R,
                    int v_layout, void* out, int out_layout);
+/* Rank-k partial pivoted Cholesky K ~= L^T L of K = k(X, X) (no noise term), matrix-free: the factor behind the
+ * MGP_PRE_LOWRANK preconditioner of the MGP_OP_KXX_NOISE system (Harbrecht et al. 2012; Gardner et al. 2018).  With
+ * d = diag K = variance, step i takes p_i = argmax_j d_j (lowest index on ties), stops with *rank_out = i if
+ * sum_j d_j <= rel_tol N variance or d_{p_i} <= 0, else writes
+ *   L[i, :] = (k(x_{p_i}, X) - sum_{j<i} L[j, p_i] L[j, :]) / sqrt(d_{p_i}),   d <- max(d - L[i, :]^2, 0),
+ * with d_{p_i} = 0 and L[i, c] = 0 exactly wherever d_c is 0 (every earlier pivot).  L [max_rank, N] row-major and
+ * piv [max_rank] (int64) are device buffers of the caller, rows and entries from *rank_out on are left untouched;
+ * diag [N] (device, may be NULL) receives the final d; rank_out is a host pointer.  Rows of K come from the kernel on
+ * the fly (direct differences, GPflow's profiles, as mgp_k_dense_vjp forms them); nothing N x N is held.  fp64 only
+ * (fp32: MGP_E_DTYPE), any D <= MGP_MAX_D, 1 <= max_rank <= 1024 (clamped to N), rel_tol >= 0, N >= 0 (N = 0: rank 0).
+ * One launch per step, the pivot never visits the host: every workgroup reduces the step partials of the launch
+ * before it, in a fixed order, so two calls give bit-identical L and piv; about 4 k^2 N bytes are streamed.
+ * Scratch, one arena of the handle (counted by mgp_workspace_bytes; MGP_E_NOMEM from a fixed pool that is too small;
+ * a growing handle rounds an arena up by a quarter): at most 8 N + 32 KiB.  Synchronises the stream. */
+int mgp_kxx_pivchol(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, int32_t max_rank, double rel_tol,
+                    void* L, int64_t* piv, void* diag, int32_t* rank_out);
+/* Z[Bt, n] = diag_inv o R - (R B^T) B for the rows of R [Bt, n], B [k, n] row-major, diag_inv [n]: one application of
+ * the MGP_PRE_LOWRANK preconditioner (fp64 and fp32; k >= 1; n = 0 or Bt = 0 writes nothing; not in place).  R B^T is
+ * reduced over n in two stages in a fixed order (no float atomics): two calls are bit-identical.  B is streamed twice
+ * per 16 rows of the batch (2 elem k n bytes; bandwidth-bound).  Scratch, the arena of mgp_kxx_pivchol:
+ * (ceil(n / c) + 1) b k elements, b = min(Bt, 16), c = 2048 / b' columns, b' = b rounded up to 1, 2, 4, 8 or 16. */
+int mgp_lowrank_apply(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
+                      const void* R, int64_t Bt, void* Z);
 /* Hyper-parameter bilinear forms of K = k(X, X) (no noise term): for theta = variance and each ARD lengthscale,
  *   dvariance = sum_r u_r^T (dK/dvariance) v_r,   dlengthscales[d] = sum_r u_r^T (dK/dl_d) v_r   (host doubles)
  * -- the gradient of the exact-GP marginal likelihood without dK/dtheta or any N x N matrix (callers fold weights into
@@ -254,7 +282,8 @@ int mgp_pcg_solve(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre,
 /* mgp_pcg_solve that also records, for every CG step k actually taken (steps gated off after convergence write
  * nothing; k < coef_steps), coef[k, b, 0:3] = (gamma, beta, 0.5 rz after the step) in the operator's dtype -- the
  * coefficients a stochastic Lanczos quadrature builds the Lanczos tridiagonal of column b from.  Preconditioner
- * MGP_PRE_EYE (or NULL) only, else MGP_E_BADARG.  The record is defined up to the first residual refresh: pass
+ * MGP_PRE_EYE (or NULL) or MGP_PRE_LOWRANK, else MGP_E_BADARG; with MGP_PRE_LOWRANK beta = (r.z)_new / (r.z)_old and T
+ * is the Lanczos tridiagonal of P^-1/2 A P^-1/2 started at P^-1/2 b.  The record is defined up to the first residual refresh: pass
  * max_steps_cycle > max_iterations.  Never takes the register-resident dense route.  coef [coef_steps, Bt, 3] device,
  * coef_steps >= 0. */
 int mgp_pcg_solve_record(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B,
