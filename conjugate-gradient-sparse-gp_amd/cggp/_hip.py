@@ -129,6 +129,7 @@ SIGNATURES = {
                                   _L, _L, _D, ctypes.c_int32, _P, _P, ctypes.POINTER(MgpCgStats), _P, _L]),
     "mgp_kxx_pivchol": (_I, [_P, _KP, _P, _L, ctypes.c_int32, _D, _P, _P, _P, ctypes.POINTER(ctypes.c_int32)]),
     "mgp_lowrank_apply": (_I, [_P, _I, _P, _P, _L, _L, _P, _L, _P]),
+    "mgp_knm_project": (_I, [_P, _KP, _P, _L, _P, _L, _P, ctypes.c_int32, _I, _P, _P]),
     # random Fourier features (cggp/rff.py)
     "mgp_rff_features": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, _L]),
     "mgp_rff_sample": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, ctypes.c_int32, _D, _P, _I]),

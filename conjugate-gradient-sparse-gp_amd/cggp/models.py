@@ -656,6 +656,101 @@ data_fit = sum y^T (K + s2 I)^-1 y, std_error = the spread of the per-probe log-
 converged of the one CG solve."""
 
 
+def _k_torch(kernel, A, B):
+    """k(A, B) in plain torch (GPflow's expansion-form distance and profiles): the CPU half of
+    `LanczosVarianceCache`, whose GPU half is libmgp's."""
+    ls = torch.as_tensor(kernel.lengthscales, dtype=A.dtype, device=A.device)
+    a, b = A / ls, B / ls
+    r2 = (a * a).sum(-1)[:, None] + (b * b).sum(-1)[None, :] - 2.0 * (a @ b.t())
+    if kernel.name == "se":
+        return kernel.variance * torch.exp(-0.5 * r2)
+    r = torch.sqrt(torch.clamp(r2, min=1e-36))
+    if kernel.name == "matern12":
+        return kernel.variance * torch.exp(-r)
+    if kernel.name == "matern32":
+        s3 = math.sqrt(3.0)
+        return kernel.variance * (1.0 + s3 * r) * torch.exp(-s3 * r)
+    s5 = math.sqrt(5.0)
+    return kernel.variance * (1.0 + s5 * r + (5.0 / 3.0) * r * r) * torch.exp(-s5 * r)
+
+
+class LanczosVarianceCache:
+    """Predictive variances of exact GP regression for whole test sets from one Lanczos run (Pleiss et al. 2018,
+    "LOVE").  k Lanczos steps on Khat = K + s2 I (`cggp.lanczos`, full re-orthogonalisation) give an orthonormal
+    Q [k, N] and a tridiagonal T = Q Khat Q^T = C C^T; with R = Q^T C^-T [N, k]
+
+        var(x*) ~= k(x*, x*) - |k(x*, X) R|^2,      cov(X*) ~= k(X*, X*) - (k(X*, X) R)(k(X*, X) R)^T.
+
+    Per test point this costs what the mean costs -- one pass over the kernel values, `mgp_knm_project` on the GPU --
+    instead of a CG solve.  It is a Galerkin projection of Khat^-1: it never under-states the variance, it decreases
+    monotonically to the exact value as the rank grows (exact at rank N), and it is capped by the prior variance.  It
+    is loose where the spectrum of K decays slowly (rough kernels, many input dimensions, short lengthscales).
+
+    `build(gpr)` runs the recurrence on `gpr.operator()` from the normalised first column of Y (`start="y"`) or from
+    a caller's vector [N]; `from_tridiagonal(Q, alpha, beta, X)` installs a hand-made basis on any device (CPU
+    included: `variance` / `covariance` are plain torch there).  `rank_` holds the rank reached (the recurrence stops
+    early when the Krylov space is exhausted)."""
+
+    def __init__(self, rank=128, start="y", breakdown=1e-10):
+        self.rank = int(rank)
+        if self.rank < 1:
+            raise ValueError("rank must be >= 1")
+        if not (isinstance(start, torch.Tensor) or start == "y"):
+            raise ValueError("start must be 'y' or a vector [N]")
+        self.start = start
+        self.breakdown = float(breakdown)
+        self.rank_ = None
+        self.X = self.R = None
+
+    def build(self, gpr):
+        from .lanczos import lanczos
+
+        X, Y = gpr.data
+        v = Y[:, 0] if isinstance(self.start, str) else self.start.to(device=X.device, dtype=X.dtype).reshape(-1)
+        if v.shape[0] != X.shape[0]:
+            raise ValueError(f"the start vector has {v.shape[0]} entries, the data {X.shape[0]} rows")
+        Q, alpha, beta = lanczos(gpr.operator(), v, self.rank, self.breakdown)
+        return self.from_tridiagonal(Q, alpha, beta, X)
+
+    def from_tridiagonal(self, Q, alpha, beta, X=None):
+        """Install the basis Q [k, N] with Q Khat Q^T = tridiag(beta, alpha, beta); X [N, D] are the training inputs
+        the queries are taken against."""
+        k = Q.shape[0]
+        if alpha.shape[0] != k or beta.shape[0] != k - 1:
+            raise ValueError(f"Q has {k} rows: alpha must be [{k}] and beta [{k - 1}]")
+        if X is not None and X.shape[0] != Q.shape[1]:
+            raise ValueError(f"Q has n={Q.shape[1]}, X has {X.shape[0]} rows")
+        T = torch.diag(alpha) + torch.diag(beta, 1) + torch.diag(beta, -1)
+        C = torch.linalg.cholesky(T)
+        # R^T = C^-1 Q through the explicit k x k inverse of the triangular factor and one GEMM: a triangular solve
+        # with N right-hand sides is not served by the BLAS at N = 2^17 (as PivotedCholeskyPreconditioner.set_factor)
+        Cinv = torch.linalg.solve_triangular(C, torch.eye(k, dtype=Q.dtype, device=Q.device), upper=False)
+        self.R = (Cinv @ Q).t().contiguous()  # [N, k]
+        self.rank_ = k
+        if X is not None:
+            self.X = X
+        return self
+
+    def _project(self, kernel, Xnew, want_proj):
+        if self.R is None or self.X is None:
+            raise RuntimeError("no basis yet: call build(gpr) or from_tridiagonal(Q, alpha, beta, X)")
+        if Xnew.is_cuda:
+            return ops.knm_project(kernel.spec(Xnew.shape[1]), Xnew, self.X, self.R, want_proj=want_proj)
+        proj = _k_torch(kernel, Xnew, self.X) @ self.R
+        return (proj * proj).sum(dim=1), proj
+
+    def variance(self, kernel, Xnew):
+        """[B]: k(x*, x*) - |k(x*, X) R|^2."""
+        sqnorm, _ = self._project(kernel, Xnew, False)
+        return kernel.K_diag(Xnew) - sqnorm
+
+    def covariance(self, kernel, Xnew):
+        """[B, B]: k(X*, X*) - (k(X*, X) R)(k(X*, X) R)^T."""
+        _, proj = self._project(kernel, Xnew, True)
+        Kss = kernel.K(Xnew) if Xnew.is_cuda else _k_torch(kernel, Xnew, Xnew)
+        return Kss - proj @ proj.t()
+
+
 class GPR:
     """Exact GP regression: GPflow `GPR`'s surface (`gpflow.models.GPR(data, kernel, noise_variance)`), the baseline the
     reference builds through `gpr_class` / `create_gpr_model` (`cggp/cli_utils.py:171-184,449-452`) and whose
@@ -667,14 +762,21 @@ class GPR:
                   alpha = (K + s2 I)^-1 y, mean = k(X*, X) alpha, and the variance solves (K + s2 I) W = K_X*
                   for the test columns in chunks of at most `variance_chunk_bytes` of K_X*.
       "auto":     Cholesky up to `cholesky_max_n` rows, CG above.
+    `variance` chooses how the CG path gets predictive variances: "solve" (default) is the per-test-column solve
+    above; "lanczos" builds a `LanczosVarianceCache` of rank `variance_rank` once per model state and answers every
+    test row from it (var = K_diag - |k(x*, X) R|^2, an upper bound that tightens with the rank; the mean is
+    unchanged).  The cache is dropped with alpha and the operator when the kernel, the noise or the data change.  On
+    the Cholesky path the option is ignored: the exact variance is cheaper there.
     `log_marginal_likelihood` needs log|K + s2 I| and exists on the Cholesky path only;
     `log_marginal_likelihood_estimate` is its matrix-free stochastic Lanczos estimate at any N.
     """
 
     def __init__(self, data, kernel, noise_variance=1.0, conjugate_gradient=None, *, solver="auto",
-                 cholesky_max_n=16384, variance_chunk_bytes=256 << 20):
+                 cholesky_max_n=16384, variance_chunk_bytes=256 << 20, variance="solve", variance_rank=128):
         if solver not in ("auto", "cholesky", "cg"):
             raise ValueError(f"unknown solver {solver!r}")
+        if variance not in ("solve", "lanczos"):
+            raise ValueError(f"unknown variance {variance!r}")
         X, Y = data
         if X.dim() != 2 or Y.dim() != 2 or Y.shape[0] != X.shape[0]:
             raise ValueError(f"data must be (X [N, D], Y [N, P]), got {tuple(X.shape)}, {tuple(Y.shape)}")
@@ -685,6 +787,8 @@ class GPR:
         self.solver = solver
         self.cholesky_max_n = int(cholesky_max_n)
         self.variance_chunk_bytes = int(variance_chunk_bytes)
+        self.variance = variance
+        self.variance_rank = int(variance_rank)
         self.invalidate()
 
     # ---- caches (alpha, the factor, the operator): functions of X, Y, the kernel and the noise, which
@@ -693,6 +797,7 @@ class GPR:
         self._L = None
         self._alpha = None
         self._op = None
+        self._variance_cache = None
         self._key = self._fingerprint()
         self._key_refs = self.data
 
@@ -701,7 +806,7 @@ class GPR:
         k = self.kernel
         return (id(X), X._version, tuple(X.shape), id(Y), Y._version, tuple(Y.shape), type(k).__name__,
                 float(k.variance), tuple(float(v) for v in k.lengthscales), float(self.likelihood.variance),
-                id(self.conjugate_gradient), self.solver, self.cholesky_max_n)
+                id(self.conjugate_gradient), self.solver, self.cholesky_max_n, self.variance, self.variance_rank)
 
     def _sync(self):
         if self._fingerprint() != self._key:
@@ -741,6 +846,13 @@ class GPR:
             self._alpha = self.solve(self.data[1])
         return self._alpha
 
+    def variance_cache(self):
+        """The `LanczosVarianceCache` of `variance="lanczos"` (built once per model state, cached)."""
+        self._sync()
+        if self._variance_cache is None:
+            self._variance_cache = LanczosVarianceCache(self.variance_rank).build(self)
+        return self._variance_cache
+
     def predict_f(self, Xnew, full_cov=False, full_output_cov=False):
         """mean [B, P]; variance [B, P] or covariance [P, B, B] (GPflow GPR.predict_f, P = 1 output here)."""
         assert not full_output_cov
@@ -760,6 +872,14 @@ class GPR:
             var = self.kernel.K_diag(Xnew) - (A * A).sum(dim=0)
             return mean, var[:, None].expand(-1, P).contiguous()
         mean = ops.knm_matvec(spec, Xnew, X, self.alpha())
+        if self.variance == "lanczos":
+            cache = self.variance_cache()
+            if full_cov:
+                cov = cache.covariance(self.kernel, Xnew)
+                cov = 0.5 * (cov + cov.t())
+                return mean, cov[None, ...].expand(P, -1, -1).contiguous()
+            var = cache.variance(self.kernel, Xnew)
+            return mean, var[:, None].expand(-1, P).contiguous()
         B, N = Xnew.shape[0], X.shape[0]
         step = max(1, min(B, self.variance_chunk_bytes // max(1, N * X.element_size())))
         if full_cov:

@@ -178,6 +178,30 @@ def lowrank_apply(diag_inv, B, R):
     return Z
 
 
+def knm_project(spec, Xs, X, R, want_proj=False, r_layout=COLS):
+    """(sqnorm [B], proj [B, r] or None): proj = k(Xs, X) @ R for a wide dense R ([N, r] COLS or [r, N] ROWS) and
+    sqnorm[b] = sum_j proj[b, j]^2, k(Xs, X) never formed on the fused route (`mgp_knm_project`: fp64, D <= 32,
+    r <= 256) -- the query of a Lanczos variance cache."""
+    Xs = _points(Xs, "Xs", spec.D)
+    X = _points(X, "X", spec.D, Xs.dtype)
+    R = _hip.check_tensor(R, "R", dtype=Xs.dtype)
+    if r_layout not in (COLS, ROWS):
+        raise ValueError(f"bad r_layout {r_layout}")
+    B, N = Xs.shape[0], X.shape[0]
+    if R.dim() != 2 or (R.shape[0] if r_layout == COLS else R.shape[1]) != N:
+        raise ValueError(f"R must be [N={N}, r] (COLS) or [r, N] (ROWS), got {tuple(R.shape)}")
+    r = R.shape[1] if r_layout == COLS else R.shape[0]
+    sqnorm = torch.empty((B,), dtype=Xs.dtype, device=Xs.device)
+    proj = torch.empty((B, r), dtype=Xs.dtype, device=Xs.device) if want_proj else None
+    if B > 0:
+        # N == 0 or r == 0 goes through the C-ABI too: libmgp writes the zeros
+        hd = _hip.get_handle(Xs.device)
+        k = spec.struct(_hip.dtype_code(Xs))
+        hd.check(hd.lib.mgp_knm_project(hd.h, ctypes.byref(k), _hip.ptr(Xs), B, _hip.ptr(X), N, _hip.ptr(R), r,
+                                        r_layout, _hip.ptr(proj), _hip.ptr(sqnorm)))
+    return sqnorm, proj
+
+
 def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e-16, check_every=10,
                      preconditioner=None):
     """CG from zero on `op` (a `conjugate_gradient.LinearOperator`) for the rows of rhs [Bt, n], no residual refresh,

@@ -334,13 +334,17 @@ class TrainableGPR:
     def training_loss(self, data=None, probes=None):
         return -self.log_marginal_likelihood(data)
 
-    def frozen_model(self):
+    def frozen_model(self, **gpr_kwargs):
+        """The trained model as a `GPR`; `variance` / `variance_rank` are forwarded to it."""
         from .models import GPR
+        unknown = set(gpr_kwargs) - {"variance", "variance_rank"}
+        if unknown:
+            raise TypeError(f"frozen_model() got unexpected keyword arguments {sorted(unknown)}")
         if self.num_probes is not None:
             return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
-                       conjugate_gradient=self.conjugate_gradient, solver="cg")
+                       conjugate_gradient=self.conjugate_gradient, solver="cg", **gpr_kwargs)
         return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
-                   solver="cholesky")
+                   solver="cholesky", **gpr_kwargs)
 
 
 def sgpr_bound(Kmm_j, Q, b, yy, s2, variance, N):

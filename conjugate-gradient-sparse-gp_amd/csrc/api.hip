@@ -130,8 +130,8 @@ extern "C" size_t mgp_workspace_bytes(const mgp_handle* h) {
   if (h->pool) return h->pool_used;
   // 256 bytes of alignment slack per arena, as a fixed pool would spend
   return h->ws_bytes + h->cg_bytes + h->opws_bytes + h->gen_bytes + h->pack[0].bytes + h->pack[1].bytes +
-         h->tri_tab_bytes + h->prof_clk_bytes + h->kxx_bytes + h->kgrad_bytes + h->pch_bytes + 8 * 256 + (h->kxx ? 256 : 0) +
-         (h->kgrad ? 256 : 0) + (h->pch ? 256 : 0);
+         h->tri_tab_bytes + h->prof_clk_bytes + h->kxx_bytes + h->kgrad_bytes + h->pch_bytes + h->prj_bytes + 8 * 256 + (h->kxx ? 256 : 0) +
+         (h->kgrad ? 256 : 0) + (h->pch ? 256 : 0) + (h->prj ? 256 : 0);
 }
 
 extern "C" int mgp_destroy(mgp_handle* h) {
@@ -147,6 +147,7 @@ extern "C" int mgp_destroy(mgp_handle* h) {
     if (h->kxx) (void)hipFree(h->kxx);
     if (h->kgrad) (void)hipFree(h->kgrad);
     if (h->pch) (void)hipFree(h->pch);
+    if (h->prj) (void)hipFree(h->prj);
     if (h->tri_tab) (void)hipFree(h->tri_tab);
     for (auto& ps : h->pack)
       if (ps.buf) (void)hipFree(ps.buf);

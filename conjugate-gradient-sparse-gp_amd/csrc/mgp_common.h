@@ -41,6 +41,10 @@ struct mgp_handle {
   // the step partials of a build, or the column-chunk partials of r B^T
   void* pch = nullptr;
   size_t pch_bytes = 0;
+  // wide projection k(Xs, X) R (project.hip): the per-split partial tiles of the fused kernel -- or, on the generic
+  // route, R^T, one row panel of k(Xs, X) and one chunk of the product
+  void* prj = nullptr;
+  size_t prj_bytes = 0;
   // generic-D scratch (transposed multipliers, kernel panel, chunk output)
   void* gen = nullptr;
   size_t gen_bytes = 0;

@@ -229,6 +229,25 @@ int mgp_kxx_pivchol(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N
  * (ceil(n / c) + 1) b k elements, b = min(Bt, 16), c = 2048 / b' columns, b' = b rounded up to 1, 2, 4, 8 or 16. */
 int mgp_lowrank_apply(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
                       const void* R, int64_t Bt, void* Z);
+/* proj[B, r] = k(Xs, X) R and sqnorm[b] = sum_j proj[b, j]^2 for a wide dense R ([N, r] MGP_COLS or [r, N] MGP_ROWS):
+ * the query of a Lanczos variance cache, var(x*) = k(x*, x*) - |k(x*, X) R|^2 with R = Q^T C^-T, T = C C^T (Pleiss et
+ * al. 2018).  proj is row-major [B, r]; either output may be NULL, not both (MGP_E_BADARG).  B = 0 writes nothing;
+ * N = 0 or r = 0 writes zeros.  k(Xs, X) is never materialised on the fused route -- fp64, D <= MGP_FUSED_MAX_D,
+ * r <= 256: a workgroup owns a tile of test rows (t = 128 for r <= 128, 64 above) and all r columns (padded to 16),
+ * evaluates each kernel value once (the expansion-form distance and profiles of mgp_kmn_knm, values as mgp_k_dense to
+ * rounding) and contracts on the fp64 matrix cores; N is split over the grid when B alone does not fill the chip and
+ * the per-split tiles are added in a fixed order by a second kernel that also forms sqnorm (csrc/project.hip; no float
+ * atomics, two calls are bit-identical).  fp32, D > 32 or r > 256: row panels of at most 256 MiB of k(Xs, X) through
+ * mgp_k_dense, the NT GEMM and a row-square-sum kernel; the same results to rounding, equally deterministic.
+ * Scratch, one arena of the handle (counted by mgp_workspace_bytes; MGP_E_NOMEM from a fixed pool that is too small; a
+ * growing handle rounds an arena up by a quarter): fused, 8 t r' (min(B', 2^16) / t + s) + 8 N (D' + 1) + 256 bytes
+ * with B' = B rounded up to t, r' = r rounded up to 16, D' = D rounded up to 2, 4, 8, 16 or 32 and s <= 4 CUs + 1 the
+ * workgroups added by the split -- at most 512 r' (1024 + 4 CUs + 1) + 8 N (D' + 1) + 256 bytes (256 CUs, r = 256:
+ * 257 MiB + O(N D)); generic, elem (r N [MGP_COLS only] + c min(N, 16384) + c r [proj NULL only]) + 256 bytes,
+ * c = min(B, max(64, 2^28 / (elem min(N, 16384)))) panel rows, and up to 8 c r elements of the NT GEMM's contraction
+ * slices in the reduction arena it shares with the other entry points. */
+int mgp_knm_project(mgp_handle* h, const mgp_kernel* k, const void* Xs, int64_t B, const void* X, int64_t N,
+                    const void* R, int32_t r, int r_layout, void* proj, void* sqnorm);
 /* Hyper-parameter bilinear forms of K = k(X, X) (no noise term): for theta = variance and each ARD lengthscale,
  *   dvariance = sum_r u_r^T (dK/dvariance) v_r,   dlengthscales[d] = sum_r u_r^T (dK/dl_d) v_r   (host doubles)
  * -- the gradient of the exact-GP marginal likelihood without dK/dtheta or any N x N matrix (callers fold weights into
