@@ -112,6 +112,10 @@ __global__ __launch_bounds__(kKxxThreads) void kxx_tile_kernel(const double* __r
   constexpr int kKxxGroup = KxxCfg<DP, RC>::G;
   constexpr double MAGIC = 0x1.8p+41;  // 2048-entry table: low word of t + MAGIC = round(2048 t)
   constexpr double kTLimit = 1000.0, kNormLimit = KIND == 0 ? kTLimit : kTLimit * kTLimit;
+  // The clamped loop writes its exact 0 only below t = -1020: the exponent add on the high word stays normal down to
+  // t = -1022, and a Matern-5/2 value is its polynomial (2^17 at q = 1000) times 2^t, so a cut at -1000 dropped values
+  // of up to variance * 2^-983 that the ldexp forms return (tests/test_gpu_pair_accuracy.py, the flush floor 2^-990).
+  constexpr double kFlushLimit = 1020.0;
   __shared__ double e2tab[MGP_EXP2_TAB_SIZE];
   __shared__ double cb[2][NROW][kKxxGroup][RC];  // per-row column sums of a group of streamed points, two buffers
 
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(kKxxThreads) void kxx_tile_kernel(const double* __r
         const double s = sv[q];
         u = s + cq[q];
         if (CLAMP) {
-          const double cmin = MAGIC - kTLimit;
+          const double cmin = MAGIC - kFlushLimit;
           low = u < cmin;
           u = low ? cmin : u;
         }
@@ -180,8 +184,8 @@ __global__ __launch_bounds__(kKxxThreads) void kxx_tile_kernel(const double* __r
         r2 = CLAMP ? (r2 < floor_r2 ? floor_r2 : r2) : __builtin_fmax(r2, floor_r2);
         double qq = mgp_sqrt_pos(r2);
         if (CLAMP) {
-          low = qq > kTLimit;
-          qq = low ? kTLimit : qq;
+          low = qq > kFlushLimit;
+          qq = low ? kFlushLimit : qq;
         }
         qv[KIND == 0 ? 0 : q] = qq;
         u = MAGIC - qq;

@@ -166,6 +166,16 @@ MGP_HD T mgp_profile(T neg_s, T clamp, E2 e2 = E2()) {
     T s = -neg_s;
     s = s < clamp ? clamp : s;  // tf.maximum(r2, 1e-36) keeps NaN: so does this form (s > clamp ? s : clamp would not)
     const T q = mgp_sqrt_pos(s);
+    if (sizeof(T) == 4 && KIND >= 2) {
+      // fp32: v_exp_f32 flushes below 2^-126, so 2^(-q) is gone at q = 126 while poly(q) 2^(-q) is still a normal number
+      // (Matern-5/2: poly = 2^11.7 at q = 138) -- values of up to variance * 2^-114 came back as 0.  Beyond q = 64 the
+      // exponent is shifted by 64 (64 - q is exact there) and the product scaled back; below it nothing changes.
+      const bool far = q > (T)64;
+      const T e = e2((far ? (T)64 : (T)0) - q);
+      const T c2 = (T)(MGP_LN2 * MGP_LN2 / 3.0);
+      const T p = KIND == 2 ? mgp_fma(q, (T)MGP_LN2, (T)1.0) : mgp_fma(mgp_fma(q, c2, (T)MGP_LN2), q, (T)1.0);
+      return (p * e) * (far ? (T)0x1p-64 : (T)1.0);
+    }
     const T e = e2(-q);
     if (KIND == 1) return e;
     if (KIND == 2) return mgp_fma(q, (T)MGP_LN2, (T)1.0) * e;

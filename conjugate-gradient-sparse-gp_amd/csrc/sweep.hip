@@ -312,7 +312,7 @@ __global__ __launch_bounds__(kThreads, (DP <= 8 && RC == 1) ? 4 : 1) void sweep_
 // = D + 8 fp64 and 3 integer instructions (and, lshl, lshl_add), one ds_read_b64 gather.
 // Valid while the exponent stays normal: t = -|a-b|^2 >= -2(|a|^2+|b|^2) > -1000 (scaled units),
 // checked per workgroup against the packed set's maximum norm; otherwise, and for NaN inputs, the
-// clamped variant of the same loop runs (2^-1000 stands for 0; NaN stays NaN).
+// clamped variant of the same loop runs (an exact 0 below t = -1020; NaN stays NaN).
 
 // Rows are formed one per thread and leave through LDS, so that the block's (DP+1)*NTP doubles are written
 // as one contiguous run (a 72-byte row per lane written in place cost 220 us for 2^20 rows; this form ~50).
@@ -449,6 +449,10 @@ __global__ __launch_bounds__(NT, DP > 16 ? (RPT == 1 ? 4 : MGP_D32_WAVES) : (RPT
   static_assert(TBITS == 11 || TBITS == 13, "table sizes: 2048 or 8192 entries");
   // the exponent must stay normal: t > -1000.  SE: t = -r^2 (scaled); Matern: t = -q, q^2 = r^2 (scaled)
   constexpr double kTLimit = 1000.0, kNormLimit = KIND == 0 ? kTLimit : kTLimit * kTLimit;
+  // The clamped loop writes its exact 0 only below t = -1020: the exponent add on the high word stays normal down to
+  // t = -1022, and a Matern-5/2 value is its polynomial (2^17 at q = 1000) times 2^t, so a cut at -1000 dropped values
+  // of up to variance * 2^-983 that the ldexp forms return (tests/test_gpu_pair_accuracy.py, the flush floor 2^-990).
+  constexpr double kFlushLimit = 1020.0;
   __shared__ double e2tab[TSIZE];
   __shared__ unsigned long long amax_w[NT / 64];
   const int t = threadIdx.x;
@@ -522,7 +526,7 @@ __global__ __launch_bounds__(NT, DP > 16 ? (RPT == 1 ? 4 : MGP_D32_WAVES) : (RPT
         const double s = sv[q];
         u = s + cq[q];
         if (CLAMP) {
-          const double cmin = MAGIC - kTLimit;
+          const double cmin = MAGIC - kFlushLimit;
           low = u < cmin;  // false for NaN: NaN flows on
           u = low ? cmin : u;
         }
@@ -534,8 +538,8 @@ __global__ __launch_bounds__(NT, DP > 16 ? (RPT == 1 ? 4 : MGP_D32_WAVES) : (RPT
         r2 = CLAMP ? (r2 < floor_r2 ? floor_r2 : r2) : __builtin_fmax(r2, floor_r2);
         double qq = mgp_sqrt_pos(r2);
         if (CLAMP) {
-          low = qq > kTLimit;
-          qq = low ? kTLimit : qq;
+          low = qq > kFlushLimit;
+          qq = low ? kFlushLimit : qq;
         }
         qv[q] = qq;
         u = MAGIC - qq;

@@ -1,5 +1,6 @@
 """References for the SGPR gradient (`mgp_kmn_knm_vjp`, `training.TrainableSGPR`): a long-double restatement of the VJP
-of (Q, B) = (K_mn K_nm, K_mn Y) with every (row, column) pair evaluated, and a torch fp64 restatement of GPflow's
+of (Q, B) = (K_mn K_nm, K_mn Y) with every (row, column) pair evaluated, the same for the VJP of a dense kernel block
+(`mgp_k_dense_vjp`), and a torch fp64 restatement of GPflow's
 `SGPR.elbo` on an explicit K_nm, differentiable in every parameter including Z."""
 
 import math
@@ -47,6 +48,30 @@ def kmn_knm_vjp_reference(name, variance, lengthscales, X, Z, Gq, Y=None, Gb=Non
         dZ += (g * diff).sum(axis=0) * coef
         sz += (ga * np.abs(diff)).sum(axis=0) * np.abs(coef)
     return dv, dl, dZ, sv, sl, sz
+
+
+def k_dense_vjp_reference(name, variance, lengthscales, A, B, G, block=256):
+    """(dvariance, dl [D]) = sum_ij G_ij dk(a_i, b_j) / d(variance, l_d) in long double (`mgp_k_dense_vjp`), every pair,
+    direct differences, and the same sums over |terms| (the scale the tests measure rounding against)."""
+    A, B, G = np.asarray(A, dtype=LD), np.asarray(B, dtype=LD), np.asarray(G, dtype=LD)
+    ls = np.asarray(lengthscales, dtype=LD).reshape(-1)
+    if ls.shape[0] == 1:
+        ls = np.repeat(ls, A.shape[1])
+    As, Bs = A / ls, B / ls
+    coef = LD(variance) * LD(-2) / ls
+    D = A.shape[1]
+    dv, dl, sv, sl = LD(0), np.zeros(D, dtype=LD), LD(0), np.zeros(D, dtype=LD)
+    for i0 in range(0, A.shape[0], block):
+        diff = As[i0:i0 + block, None, :] - Bs[None, :, :]
+        d2 = diff * diff
+        f, fp = _profile(name, d2.sum(axis=2))
+        Gb = G[i0:i0 + block]
+        dv += np.sum(Gb * f)
+        sv += np.sum(np.abs(Gb * f))
+        w = (Gb * fp)[:, :, None] * d2 * coef
+        dl += w.sum(axis=(0, 1))
+        sl += np.abs(w).sum(axis=(0, 1))
+    return dv, dl, sv, sl
 
 
 def kernel_torch(name, variance, lengthscales, A, B):

@@ -12,6 +12,8 @@ symmetric products (test_symm_matmul_fp64 / test_symm_gemv_upper_triangle_path),
 keeps the summation order, so its result must also equal the default handle's bit for bit.
 """
 
+import contextlib
+
 KINDS = ("se", "matern12", "matern32", "matern52")
 NUM_CUS = 256  # MI355X
 
@@ -213,6 +215,29 @@ FORMS = [
          routes="cg.hip: coll && !fuse_agree -> put_gate_word_kernel and finish_allreduce_kernel as launches of their own",
          ref="the fused form and the no-collective solve", bar="bitwise"),
 ]
+
+
+@contextlib.contextmanager
+def switched(monkeypatch, env):
+    """A handle made under `env`, installed as the handle of device 0 for the duration (GPU tests only: torch and
+    the library are imported here, so that the CPU inventory test can read the table without them)."""
+    import torch
+
+    from cggp import _hip
+    _hip.get_handle(torch.device("cuda:0"))  # the default handle exists first, so it can be restored
+    prev = _hip._handles.get(0)
+    with monkeypatch.context() as mp:
+        for k, v in env.items():
+            mp.setenv(k, v)
+        hd = _hip.Handle(0)
+        _hip._handles[0] = hd
+        try:
+            yield hd
+        finally:
+            torch.cuda.synchronize()
+            _hip._handles[0] = prev
+            hd.lib.mgp_destroy(hd.h)
+            hd.h = None
 
 
 def table_switches():

@@ -8,7 +8,6 @@ handle's result bit for bit.  Last, the fused k^2 column sum (default handle), w
 preconditioner, against the long-double sum.
 """
 
-import contextlib
 import ctypes
 import types
 
@@ -61,24 +60,7 @@ def product_bar(name):
     return 1e-9 if name == "matern12" else 1e-11
 
 
-@contextlib.contextmanager
-def switched(monkeypatch, env):
-    """A handle made under `env`, installed as the handle of device 0 for the duration."""
-    from cggp import _hip
-    _hip.get_handle(dev())  # the default handle exists first, so it can be restored
-    prev = _hip._handles.get(0)
-    with monkeypatch.context() as mp:
-        for k, v in env.items():
-            mp.setenv(k, v)
-        hd = _hip.Handle(0)
-        _hip._handles[0] = hd
-        try:
-            yield hd
-        finally:
-            torch.cuda.synchronize()
-            _hip._handles[0] = prev
-            hd.lib.mgp_destroy(hd.h)
-            hd.h = None
+switched = sf.switched  # the context manager lives beside the table: tests/test_gpu_pair_accuracy.py runs its probes under the same rows
 
 
 def rows_of(kind):

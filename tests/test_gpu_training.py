@@ -81,6 +81,36 @@ def test_k_dense_vjp_any_dimension(name, D):
     assert abs(dvar32 - dvar) < 2e-4 * max(1.0, abs(dvar)) and np.max(np.abs(np.asarray(dls32) - dls)) < 2e-4 * scale
 
 
+@pytest.mark.parametrize("name", KINDS)
+@pytest.mark.parametrize("D", [1, 3, 8, 17, 32, 33, 77, 90])
+def test_k_dense_vjp_against_long_double(name, D):
+    """The full-sum VJP (grad.hip; the tile-wise reduction of generic.hip above D = 32) against a long-double
+    restatement over every pair, at the bar of test_kmn_knm_vjp_against_long_double: 1e-10 of the sum of |terms| for
+    dvariance and each dl_d; fp32 at the 2e-4 of the fp32 line above, of the same scale.  Ragged shapes, one row, one
+    column; coincident pairs for the Matern kinds (the floor: f' = 0 there)."""
+    from cggp import ops
+    from sgpr_grad_reference import k_dense_vjp_reference
+    for na, nb in [(777, 130), (1, 37), (5000, 1)]:
+        rng = np.random.default_rng(na + 7 * nb + D)
+        A, B = rng.standard_normal((na, D)), rng.standard_normal((nb, D)) + 0.3
+        if name != "se":
+            ndup = min(na, nb) // 8 + 1
+            B[:ndup] = A[:ndup]
+        G = rng.standard_normal((na, nb))
+        ls = np.linspace(0.7, 1.3, D) * np.sqrt(D)
+        spec = ops.KernelSpec(name, 1.4, ls.tolist(), D)
+        rv, rl, sv, sl = k_dense_vjp_reference(name, 1.4, ls, A, B, G)
+        rv, sv, rl, sl = float(rv), float(sv), rl.astype(np.float64), sl.astype(np.float64)
+        for dtype, bar in ((torch.float64, 1e-10), (torch.float32, 2e-4)):
+            dv, dl = ops.k_dense_vjp(spec, T(A).to(dtype), T(B).to(dtype), T(G).to(dtype))
+            dl = np.asarray(dl)
+            assert np.isfinite(dv) and np.all(np.isfinite(dl)), (na, nb, dtype)
+            print(f"k_dense_vjp {name} D={D} {na}x{nb} {dtype}: dvariance err / sum|terms| {abs(dv - rv) / sv:.2e}, "
+                  f"dl worst {np.max(np.abs(dl - rl) / sl):.2e}")
+            assert abs(dv - rv) <= bar * sv, (na, nb, dtype, dv, rv, sv)
+            assert np.all(np.abs(dl - rl) <= bar * sl), (na, nb, dtype, np.max(np.abs(dl - rl) / sl))
+
+
 @pytest.mark.parametrize("D", [33, 77])
 def test_elbo_gradient_any_dimension(D):
     """The ELBO gradient through CG with D > 32 inputs against finite differences of the oracle's Cholesky twin."""
