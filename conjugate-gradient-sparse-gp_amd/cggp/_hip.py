@@ -101,6 +101,7 @@ SIGNATURES = {
     "mgp_create": (_I, [ctypes.POINTER(_P), _I]),
     "mgp_create_ex": (_I, [ctypes.POINTER(_P), _I, ctypes.c_size_t]),
     "mgp_workspace_bytes": (ctypes.c_size_t, [_P]),
+    "mgp_arena_bytes": (ctypes.c_size_t, [_P, ctypes.c_char_p]),
     "mgp_destroy": (_I, [_P]),
     "mgp_set_stream": (_I, [_P, _P]),
     "mgp_last_error": (ctypes.c_char_p, [_P]),
@@ -259,6 +260,8 @@ def check_tensor(t, name, dtype=None, shape=None):
     if shape is not None:
         if t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
             raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {shape}")
+    # a contiguous row slice (X[i0:i1], a rank's shard) keeps its base: element-aligned, not 16-byte aligned, which is
+    # all include/mgp.h asks for (tests/test_gpu_buffer_contract.py runs every entry point at such a base)
     return t.contiguous()
 
 

@@ -134,6 +134,17 @@ extern "C" size_t mgp_workspace_bytes(const mgp_handle* h) {
          (h->kgrad ? 256 : 0) + (h->pch ? 256 : 0) + (h->prj ? 256 : 0);
 }
 
+extern "C" size_t mgp_arena_bytes(const mgp_handle* h, const char* name) {
+  if (!h || !name) return 0;
+  const struct { const char* n; size_t b; } t[] = {
+      {"ws", h->ws_bytes},     {"cg", h->cg_bytes},   {"opws", h->opws_bytes}, {"kxx", h->kxx_bytes},
+      {"kgrad", h->kgrad_bytes}, {"pch", h->pch_bytes}, {"prj", h->prj_bytes},   {"gen", h->gen_bytes},
+      {"pack", h->pack[0].bytes + h->pack[1].bytes}};
+  for (const auto& e : t)
+    if (strcmp(name, e.n) == 0) return e.b;
+  return 0;
+}
+
 extern "C" int mgp_destroy(mgp_handle* h) {
   if (!h) return MGP_OK;
   (void)hipSetDevice(h->device);

@@ -744,7 +744,7 @@ __global__ __launch_bounds__(512) void symm_skinny_kernel(const T* __restrict__ 
   Acc acc[NBT];
 #pragma unroll
   for (int bt = 0; bt < NBT; ++bt) acc[bt] = Acc{0, 0, 0, 0};
-  const bool vec = (n & 3) == 0;
+  const bool vec = (n & 3) == 0 && (((uintptr_t)A) % (4 * sizeof(T))) == 0;  // naturally aligned 4-element loads
   // software pipeline: the operands of slab k+1 are in flight while slab k runs on the matrix core
   T a[4], an[4];
   T p[NBT][4], pn[NBT][4];
@@ -1414,7 +1414,8 @@ int symm_gemv_rows_t(mgp_handle* h, const T* A, long n, const T* p, long rb, lon
   const bool vec = (n % VECW) == 0 && (((uintptr_t)A) % 16) == 0;
   if ((re - rb) <= 2L * h->num_cus * 4 && n >= 1024) {  // a rank's slab: columns split over the waves of a workgroup
     dim3 grid((unsigned)((re - rb + 1) / 2));
-    if (vec && (n % (64 * VECW)) == 0)
+    // the slab kernel loads p through the same 16-byte vectors as the rows of A
+    if (vec && (n % (64 * VECW)) == 0 && (((uintptr_t)p) % 16) == 0)
       hipLaunchKernelGGL((symm_gemv_slab_kernel<T, VECW>), grid, dim3(256), 0, h->stream, A, n, p, out, gate, rb, re,
                          alpha, word);
     else

@@ -10,7 +10,13 @@
  *
  * Conventions
  *  - plain pointers and sizes only; every data pointer is a DEVICE pointer unless a
- *    parameter says "host"; row-major, contiguous, 16-byte aligned base.
+ *    parameter says "host"; row-major, contiguous, base aligned to the element size (8 bytes
+ *    fp64 / int64, 4 bytes fp32): any contiguous slice of an allocation is a valid argument.  A
+ *    wider alignment is never required; where a kernel has a 16- or 32-byte vector form, the host
+ *    selects it only when every pointer it loads through is so aligned (csrc/dense.hip), and the
+ *    result meets the same bound either way.  Writes stay inside the documented extent of an
+ *    output and inputs are never modified (tests/test_gpu_buffer_contract.py checks every entry
+ *    point at both alignments between guard bands).
  *  - the caller owns every buffer it passes.  The library owns only its handle and a
  *    device workspace that it grows on demand (never while a stream capture is active).
  *  - every function returns 0 on success or a negative MGP_E_* code and never throws or
@@ -161,6 +167,10 @@ int mgp_create(mgp_handle** out, int device);
  * growing handle, read it, and create the production handle with that figure. */
 int mgp_create_ex(mgp_handle** out, int device, size_t workspace_bytes);
 size_t mgp_workspace_bytes(const mgp_handle* h);
+/* Diagnosis: bytes one reused arena of the handle holds now -- "ws", "cg", "opws", "kxx", "kgrad", "pch", "prj", "gen" or
+ * "pack" (both slots); 0 for any other name.  An arena that a call reserved from is non-zero afterwards (growing handle
+ * and fixed pool alike), which is how tests/test_gpu_buffer_contract.py knows which arenas an entry point reaches. */
+size_t mgp_arena_bytes(const mgp_handle* h, const char* name);
 int mgp_destroy(mgp_handle* h);
 int mgp_set_stream(mgp_handle* h, void* hip_stream);
 const char* mgp_last_error(mgp_handle* h);
