@@ -261,13 +261,6 @@ extern "C" int mgp_profile_read_clocks(mgp_handle* h, double* mhz_out, int64_t c
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // out[c] = sum_r A[r,c]*B[r,c]: block = 64 columns x 4 row-slices, rows summed in fixed order
 template <typename T>
 __global__ __launch_bounds__(256) void colwise_dot_kernel(const T* __restrict__ A, const T* __restrict__ B,
@@ -291,7 +284,7 @@ __global__ __launch_bounds__(256) void dot_partial_kernel(const T* __restrict__ 
   double s = 0;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256)
     s += (double)A[i] * (double)B[i];
-  s = wave_sum(s);
+  s = mgp_wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -307,12 +300,12 @@ extern "C" int mgp_colwise_dot(mgp_handle* h, int dtype, const void* A, const vo
   if (cols == 0) return MGP_OK;
   if (!out || (rows > 0 && (!A || !B))) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   dim3 grid((unsigned)((cols + 63) / 64));
-  if (dtype == MGP_F64)
-    hipLaunchKernelGGL((colwise_dot_kernel<double>), grid, dim3(256), 0, h->stream, (const double*)A,
-                       (const double*)B, rows, cols, (double*)out);
-  else
-    hipLaunchKernelGGL((colwise_dot_kernel<float>), grid, dim3(256), 0, h->stream, (const float*)A,
-                       (const float*)B, rows, cols, (float*)out);
+  mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((colwise_dot_kernel<T>), grid, dim3(256), 0, h->stream, (const T*)A, (const T*)B, rows, cols,
+                       (T*)out);
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
 }
@@ -327,12 +320,11 @@ extern "C" int mgp_dot_all(mgp_handle* h, int dtype, const void* A, const void* 
   const int nb = 512;
   MGP_TRY(mgp_reserve(h, &h->ws, &h->ws_bytes, nb * sizeof(double)));
   double* part = (double*)h->ws;
-  if (dtype == MGP_F64)
-    hipLaunchKernelGGL((dot_partial_kernel<double>), dim3(nb), dim3(256), 0, h->stream, (const double*)A,
-                       (const double*)B, count, part);
-  else
-    hipLaunchKernelGGL((dot_partial_kernel<float>), dim3(nb), dim3(256), 0, h->stream, (const float*)A,
-                       (const float*)B, count, part);
+  mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((dot_partial_kernel<T>), dim3(nb), dim3(256), 0, h->stream, (const T*)A, (const T*)B, count, part);
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
   double host[512];
   MGP_HIP(h, hipMemcpyAsync(host, part, nb * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -25,8 +25,7 @@ using CgCtrl = MgpCgCtrl;  // mgp_common.h (shared with cg_dense1.hip)
 
 template <typename T>
 __device__ __forceinline__ T block_sum(T v, T* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  v = mgp_wave_sum(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __syncthreads();  // red reuse
   if (lane == 0) red[wave] = v;
@@ -239,8 +238,7 @@ __global__ __launch_bounds__(NT) void cg_update_fused_kernel(CgCtrl* __restrict_
   }
 #pragma unroll
   for (int e = 0; e < EPT; ++e) d = mgp_fma(pv[e], av[e], d);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+  d = mgp_wave_sum(d);
   if (lane == 0) red[0][wave] = d;
   __syncthreads();
   d = 0;
@@ -258,11 +256,8 @@ __global__ __launch_bounds__(NT) void cg_update_fused_kernel(CgCtrl* __restrict_
     s_rz = mgp_fma(zv[e], rv[e], s_rz);
     s_rr = mgp_fma(rv[e], rv[e], s_rr);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s_rz += __shfl_xor(s_rz, o, 64);
-    s_rr += __shfl_xor(s_rr, o, 64);
-  }
+  s_rz = mgp_wave_sum(s_rz);
+  s_rr = mgp_wave_sum(s_rr);
   __syncthreads();  // red[0] fully read
   if (lane == 0) {
     red[0][wave] = s_rz;
@@ -869,13 +864,11 @@ int pcg_solve_entry(mgp_handle* h, const mgp_operator* op, const mgp_precond* pr
   if (max_steps_cycle < 1) return mgp_fail(h, MGP_E_BADARG, "max_steps_cycle < 1");
   if (Bt > 2147483647L) return mgp_fail(h, MGP_E_SHAPE, "Bt too large");
   auto run = [&]() -> int {
-    if (op->dtype == MGP_F64)
-      return pcg_solve_t<double>(h, op, pre, (const double*)B, (const double*)V0, Bt, error_threshold, max_iterations,
-                                 max_steps_cycle, min_float, check_every, (double*)V_out, (double*)err_out, stats,
-                                 (double*)coef, coef_steps);
-    return pcg_solve_t<float>(h, op, pre, (const float*)B, (const float*)V0, Bt, error_threshold, max_iterations,
-                              max_steps_cycle, min_float, check_every, (float*)V_out, (float*)err_out, stats,
-                              (float*)coef, coef_steps);
+    return mgp_with_dtype(op->dtype, [&](auto t) {
+      using T = decltype(t);
+      return pcg_solve_t<T>(h, op, pre, (const T*)B, (const T*)V0, Bt, error_threshold, max_iterations, max_steps_cycle,
+                            min_float, check_every, (T*)V_out, (T*)err_out, stats, (T*)coef, coef_steps);
+    });
   };
   int rc = run();
   if (rc == kRetryWithoutPersist) {
@@ -922,8 +915,10 @@ extern "C" int mgp_operator_apply(mgp_handle* h, const mgp_operator* op, const v
   MGP_TRY(check_operator(h, op));
   if (Bt <= 0) return Bt == 0 ? MGP_OK : mgp_fail(h, MGP_E_SHAPE, "Bt < 0");
   if (!P || !out) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
-  if (op->dtype == MGP_F64) return apply_operator<double>(h, op, (const double*)P, Bt, (double*)out, nullptr);
-  return apply_operator<float>(h, op, (const float*)P, Bt, (float*)out, nullptr);
+  return mgp_with_dtype(op->dtype, [&](auto t) {
+    using T = decltype(t);
+    return apply_operator<T>(h, op, (const T*)P, Bt, (T*)out, nullptr);
+  });
 }
 
 // Named form of the matrix-free (Kmm + Lambda) product (SURVEY 8b lists it as its own entry point):

@@ -162,55 +162,41 @@ __global__ __launch_bounds__(NT) void cluster_reduce_kernel(const T* __restrict_
   counts[m] = c;
 }
 
-template <typename T, int KIND>
-int nearest_dp(mgp_handle* h, const SweepParams& prm, int D, int dist_type, const T* X, long N, const T* Z, long M,
-               long* idx, T* best) {
-  // rows per thread: as many as still leave two workgroups per CU (C2's 10^5 rows stay at one)
-  int rpt = D <= 8 ? 4 : 2;
-  while (rpt > 1 && (N + (long)NT * rpt - 1) / ((long)NT * rpt) < 2L * h->num_cus) rpt >>= 1;
-  dim3 grid((unsigned)((N + (long)NT * rpt - 1) / ((long)NT * rpt)));
-#define MGP_NC1(DPV, RV)                                                                                        \
-  do {                                                                                                          \
-    if (dist_type == 1)                                                                                         \
-      hipLaunchKernelGGL((nearest_kernel<T, DPV, KIND, RV, true>), grid, dim3(NT), 0, h->stream, X, N, Z, M, D, prm, \
-                         dist_type, idx, best);                                                                 \
-    else                                                                                                        \
-      hipLaunchKernelGGL((nearest_kernel<T, DPV, KIND, RV, false>), grid, dim3(NT), 0, h->stream, X, N, Z, M, D,  \
-                         prm, dist_type, idx, best);                                                            \
-  } while (0)
-#define MGP_NC(DPV)          \
-  do {                       \
-    if (rpt == 4) {          \
-      if (DPV <= 8) MGP_NC1(DPV, 4); \
-    } else if (rpt == 2)     \
-      MGP_NC1(DPV, 2);       \
-    else                     \
-      MGP_NC1(DPV, 1);       \
-  } while (0)
-  if (D <= 2) MGP_NC(2);
-  else if (D <= 4) MGP_NC(4);
-  else if (D <= 8) MGP_NC(8);
-  else if (D <= 16) MGP_NC(16);
-  else MGP_NC(32);
-#undef MGP_NC1
-#undef MGP_NC
-  MGP_LAUNCH_CHECK(h);
-  return MGP_OK;
-}
-
 template <typename T>
 int nearest_t(mgp_handle* h, const mgp_kernel* k, int dist_type, const T* X, long N, const T* Z, long M, long* idx,
               T* best) {
   SweepParams prm = mgp_make_params(k);
+  const int D = k->D;
   if (dist_type <= 1) {  // raw inputs: no lengthscale, no profile scale
-    for (int d = 0; d < MGP_FUSED_MAX_D; ++d) prm.inv_ls[d] = d < k->D ? 1.0 : 0.0;
+    for (int d = 0; d < MGP_FUSED_MAX_D; ++d) prm.inv_ls[d] = d < D ? 1.0 : 0.0;
   }
-  switch (k->kind) {
-    case MGP_SE: return nearest_dp<T, 0>(h, prm, k->D, dist_type, X, N, Z, M, idx, best);
-    case MGP_MATERN12: return nearest_dp<T, 1>(h, prm, k->D, dist_type, X, N, Z, M, idx, best);
-    case MGP_MATERN32: return nearest_dp<T, 2>(h, prm, k->D, dist_type, X, N, Z, M, idx, best);
-    default: return nearest_dp<T, 3>(h, prm, k->D, dist_type, X, N, Z, M, idx, best);
-  }
+  // rows per thread: as many as still leave two workgroups per CU (C2's 10^5 rows stay at one)
+  int rpt = D <= 8 ? 4 : 2;
+  while (rpt > 1 && (N + (long)NT * rpt - 1) / ((long)NT * rpt) < 2L * h->num_cus) rpt >>= 1;
+  dim3 grid((unsigned)((N + (long)NT * rpt - 1) / ((long)NT * rpt)));
+  mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp(D, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      auto launch = [&](auto rv, auto direct) {
+        hipLaunchKernelGGL((nearest_kernel<T, DP, decltype(kind)::value, decltype(rv)::value, decltype(direct)::value>),
+                           grid, dim3(NT), 0, h->stream, X, N, Z, M, D, prm, dist_type, idx, best);
+      };
+      auto with_direct = [&](auto rv) {
+        if (dist_type == 1) launch(rv, std::true_type{});
+        else launch(rv, std::false_type{});
+      };
+      if (rpt == 4) {
+        if constexpr (DP <= 8) with_direct(std::integral_constant<int, 4>{});  // rpt is 4 only at D <= 8
+      } else if (rpt == 2) {
+        with_direct(std::integral_constant<int, 2>{});
+      } else {
+        with_direct(std::integral_constant<int, 1>{});
+      }
+      return MGP_OK;
+    });
+  });
+  MGP_LAUNCH_CHECK(h);
+  return MGP_OK;
 }
 
 template <typename T>
@@ -251,8 +237,7 @@ __global__ __launch_bounds__(256) void segment_sums_kernel(const long* __restric
   for (long c = 0; c < C; ++c) {
     T s = 0;
     for (long i = lo + lane; i < hi; i += 64) s += Y[order[i] * C + c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = mgp_wave_sum(s);
     if (lane == 0) sums[m * C + c] = s;
   }
 }
@@ -266,12 +251,12 @@ extern "C" int mgp_segment_sums(mgp_handle* h, int dtype, const int64_t* order, 
   if (N < 0 || M <= 0 || C <= 0) return mgp_fail(h, MGP_E_SHAPE, "segment_sums: bad shape");
   if (!offsets || !sums || (N > 0 && (!order || !Y))) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   dim3 grid((unsigned)((M + 3) / 4));
-  if (dtype == MGP_F64)
-    hipLaunchKernelGGL((segment_sums_kernel<double>), grid, dim3(256), 0, h->stream, (const long*)order,
-                       (const long*)offsets, (const double*)Y, (long)C, (long)M, (double*)sums);
-  else
-    hipLaunchKernelGGL((segment_sums_kernel<float>), grid, dim3(256), 0, h->stream, (const long*)order,
-                       (const long*)offsets, (const float*)Y, (long)C, (long)M, (float*)sums);
+  mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((segment_sums_kernel<T>), grid, dim3(256), 0, h->stream, (const long*)order,
+                       (const long*)offsets, (const T*)Y, (long)C, (long)M, (T*)sums);
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
 }
@@ -284,9 +269,10 @@ extern "C" int mgp_nearest_center(mgp_handle* h, const mgp_kernel* k, int dist_t
   if (N == 0) return MGP_OK;
   if (!X || !Z || !idx) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   if (k->D > MGP_FUSED_MAX_D) return mgp_nearest_generic(h, k, dist_type, X, N, Z, M, idx, best);  // generic.hip
-  if (k->dtype == MGP_F64)
-    return nearest_t<double>(h, k, dist_type, (const double*)X, N, (const double*)Z, M, (long*)idx, (double*)best);
-  return nearest_t<float>(h, k, dist_type, (const float*)X, N, (const float*)Z, M, (long*)idx, (float*)best);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return nearest_t<T>(h, k, dist_type, (const T*)X, N, (const T*)Z, M, (long*)idx, (T*)best);
+  });
 }
 
 extern "C" int mgp_cluster_stats(mgp_handle* h, int dtype, const int64_t* idx, const void* y, int64_t N,
@@ -300,7 +286,8 @@ extern "C" int mgp_cluster_stats(mgp_handle* h, int dtype, const int64_t* idx, c
     MGP_HIP(h, hipMemsetAsync(counts, 0, (size_t)M * mgp_elem(dtype), h->stream));
     return MGP_OK;
   }
-  if (dtype == MGP_F64)
-    return cluster_stats_t<double>(h, (const long*)idx, (const double*)y, N, M, (double*)sums, (double*)counts);
-  return cluster_stats_t<float>(h, (const long*)idx, (const float*)y, N, M, (float*)sums, (float*)counts);
+  return mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return cluster_stats_t<T>(h, (const long*)idx, (const T*)y, N, M, (T*)sums, (T*)counts);
+  });
 }

@@ -156,8 +156,10 @@ __global__ __launch_bounds__(256) void kmn_knm_reduce_kernel(const T* __restrict
   }
 }
 
-template <typename T, int KIND>
-int kmn_knm_dp(mgp_handle* h, const SweepParams& prm, int D, const T* X, long N, const T* Z, long M, T* out) {
+template <typename T>
+int kmn_knm_t(mgp_handle* h, const mgp_kernel* k, const T* X, long N, const T* Z, long M, T* out) {
+  const SweepParams prm = mgp_make_params(k);
+  const int D = k->D;
   const int nt = (int)((M + CT - 1) / CT);
   const int ntiles = nt * (nt + 1) / 2;
   long nsplit = (4L * h->num_cus + ntiles - 1) / ntiles;
@@ -187,31 +189,18 @@ int kmn_knm_dp(mgp_handle* h, const SweepParams& prm, int D, const T* X, long N,
   MGP_HIP(h, hipMemcpyAsync(tab_dev, tp, tab_bytes, hipMemcpyHostToDevice, h->stream));
   MGP_HIP(h, hipStreamSynchronize(h->stream));  // tab is a host temporary
   dim3 grid((unsigned)ntiles, 1, (unsigned)nsplit);
-#define MGP_CT(DPV)                                                                                          \
-  hipLaunchKernelGGL((kmn_knm_kernel<T, DPV, KIND>), grid, dim3(256), 0, h->stream, X, N, Z, M, part, rows, D, \
-                     prm, (const int*)tab_dev)
-  if (D <= 2) MGP_CT(2);
-  else if (D <= 4) MGP_CT(4);
-  else if (D <= 8) MGP_CT(8);
-  else if (D <= 16) MGP_CT(16);
-  else MGP_CT(32);
-#undef MGP_CT
+  mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp(D, [&](auto dp) {
+      hipLaunchKernelGGL((kmn_knm_kernel<T, decltype(dp)::value, decltype(kind)::value>), grid, dim3(256), 0, h->stream,
+                         X, N, Z, M, part, rows, D, prm, (const int*)tab_dev);
+      return MGP_OK;
+    });
+  });
   MGP_LAUNCH_CHECK(h);
   hipLaunchKernelGGL((kmn_knm_reduce_kernel<T>), dim3((unsigned)ntiles), dim3(256), 0, h->stream, (const T*)part,
                      (int)nsplit, ntiles, (const int*)tab_dev, M, out, (T)(prm.variance * prm.variance));
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
-}
-
-template <typename T>
-int kmn_knm_t(mgp_handle* h, const mgp_kernel* k, const T* X, long N, const T* Z, long M, T* out) {
-  const SweepParams prm = mgp_make_params(k);
-  switch (k->kind) {
-    case MGP_SE: return kmn_knm_dp<T, 0>(h, prm, k->D, X, N, Z, M, out);
-    case MGP_MATERN12: return kmn_knm_dp<T, 1>(h, prm, k->D, X, N, Z, M, out);
-    case MGP_MATERN32: return kmn_knm_dp<T, 2>(h, prm, k->D, X, N, Z, M, out);
-    default: return kmn_knm_dp<T, 3>(h, prm, k->D, X, N, Z, M, out);
-  }
 }
 
 }  // namespace
@@ -279,6 +268,8 @@ extern "C" int mgp_kmn_knm(mgp_handle* h, const mgp_kernel* k, const void* X, in
     const char* mode = getenv("MGP_CONTRACT");  // "fused" keeps the single-kernel form for A/B runs
     if (k->D > MGP_FUSED_MAX_D || !(mode && strcmp(mode, "fused") == 0)) return kmn_knm_two_stage(h, k, X, N, Z, M, out);
   }
-  if (k->dtype == MGP_F64) return kmn_knm_t<double>(h, k, (const double*)X, N, (const double*)Z, M, (double*)out);
-  return kmn_knm_t<float>(h, k, (const float*)X, N, (const float*)Z, M, (float*)out);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return kmn_knm_t<T>(h, k, (const T*)X, N, (const T*)Z, M, (T*)out);
+  });
 }

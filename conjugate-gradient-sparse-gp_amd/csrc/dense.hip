@@ -74,51 +74,30 @@ __global__ __launch_bounds__(256) void k_dense_kernel(const T* __restrict__ A, l
   }
 }
 
-template <typename T, int KIND>
-int k_dense_dp(mgp_handle* h, const SweepParams& prm, int D, const T* A, long na, const T* B, long nb, T* out,
-               long ld, T jitter, const T* diag_add) {
-  // rows of A per block: 64 when a B point is expensive to load (D > 8) or there are enough blocks anyway
-  const int ta = (h->kdense_ta > 0) ? h->kdense_ta : ((D > 8 && na >= 64) ? 64 : 16);
-  dim3 grid((unsigned)((nb + 255) / 256), (unsigned)((na + ta - 1) / ta));
-#define MGP_KD(DPV)                                                                                                  \
-  do {                                                                                                               \
-    if (ta == 64)                                                                                                    \
-      hipLaunchKernelGGL((k_dense_kernel<T, DPV, KIND, 64>), grid, dim3(256), 0, h->stream, A, na, B, nb, out, ld, D, \
-                         prm, jitter, diag_add);                                                                     \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_dense_kernel<T, DPV, KIND, 16>), grid, dim3(256), 0, h->stream, A, na, B, nb, out, ld, D, \
-                         prm, jitter, diag_add);                                                                     \
-  } while (0)
-  if (D <= 2) MGP_KD(2);
-  else if (D <= 4) MGP_KD(4);
-  else if (D <= 8) MGP_KD(8);
-  else if (D <= 16) MGP_KD(16);
-  else MGP_KD(32);
-#undef MGP_KD
-  MGP_LAUNCH_CHECK(h);
-  return MGP_OK;
-}
-
 template <typename T>
 int k_dense_t(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const T* B, long nb, T* out, long ld,
               double jitter, const T* diag_add) {
   const SweepParams prm = mgp_make_params(k);
-  switch (k->kind) {
-    case MGP_SE: return k_dense_dp<T, 0>(h, prm, k->D, A, na, B, nb, out, ld, (T)jitter, diag_add);
-    case MGP_MATERN12: return k_dense_dp<T, 1>(h, prm, k->D, A, na, B, nb, out, ld, (T)jitter, diag_add);
-    case MGP_MATERN32: return k_dense_dp<T, 2>(h, prm, k->D, A, na, B, nb, out, ld, (T)jitter, diag_add);
-    default: return k_dense_dp<T, 3>(h, prm, k->D, A, na, B, nb, out, ld, (T)jitter, diag_add);
-  }
+  const int D = k->D;
+  // rows of A per block: 64 when a B point is expensive to load (D > 8) or there are enough blocks anyway
+  const int ta = (h->kdense_ta > 0) ? h->kdense_ta : ((D > 8 && na >= 64) ? 64 : 16);
+  dim3 grid((unsigned)((nb + 255) / 256), (unsigned)((na + ta - 1) / ta));
+  mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp(D, [&](auto dp) {
+      auto launch = [&](auto tav) {
+        hipLaunchKernelGGL((k_dense_kernel<T, decltype(dp)::value, decltype(kind)::value, decltype(tav)::value>), grid,
+                           dim3(256), 0, h->stream, A, na, B, nb, out, ld, D, prm, (T)jitter, diag_add);
+      };
+      if (ta == 64) launch(std::integral_constant<int, 64>{});
+      else launch(std::integral_constant<int, 16>{});
+      return MGP_OK;
+    });
+  });
+  MGP_LAUNCH_CHECK(h);
+  return MGP_OK;
 }
 
 // ------------------------------------------------------------------ GEMV (one right-hand side)
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // one wave per RW rows of A; lanes stride the row in VEC-element pieces (RW*VEC*sizeof(T)*64 bytes
 // of A in flight per wave and loop trip, unrolled by 2)
 template <typename T, int BT, int VEC>
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(256) void symm_gemv_kernel(const T* __restrict__ A,
   for (int q = 0; q < RW; ++q)
 #pragma unroll
     for (int b = 0; b < BT; ++b) {
-      const T s = wave_sum(acc[q][b]);
+      const T s = mgp_wave_sum(acc[q][b]);
       if (lane == 0 && b < bt && row0 + q < row_end) {
         T* o = &out[(long)b * n + row0 + q];
         *o = accumulate ? mgp_fma(alpha, s, *o) : s;
@@ -220,8 +199,8 @@ __global__ __launch_bounds__(256) void symm_gemv_slab_kernel(const T* __restrict
       }
     }
   }
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
+  s0 = mgp_wave_sum(s0);
+  s1 = mgp_wave_sum(s1);
   if (lane == 0) {
     part[wave][0] = s0;
     part[wave][1] = s1;
@@ -1468,11 +1447,10 @@ int mgp_symm_gemv_tri_prepare(mgp_handle* h, int dtype, int64_t n, void** Q, con
 
 int mgp_symm_gemv_rows_acc(mgp_handle* h, int dtype, const void* A, int64_t n, const void* p, int64_t rb, int64_t re,
                            double alpha, void* out, const int* gate, void* word) {
-  if (dtype == MGP_F64)
-    return symm_gemv_rows_t<double>(h, (const double*)A, n, (const double*)p, rb, re, alpha, (double*)out, gate,
-                                    (double*)word);
-  return symm_gemv_rows_t<float>(h, (const float*)A, n, (const float*)p, rb, re, (float)alpha, (float*)out, gate,
-                                 (float*)word);
+  return mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return symm_gemv_rows_t<T>(h, (const T*)A, n, (const T*)p, rb, re, (T)alpha, (T*)out, gate, (T*)word);
+  });
 }
 
 // out[n, n] (+)= Kt[n, K] . Kt[n, K]^T on upper-triangular tiles (contract.hip accumulates row chunks)
@@ -1500,21 +1478,20 @@ int mgp_syrk_nt_upper(mgp_handle* h, int dtype, const void* Kt, int64_t n, int64
 
 int mgp_gemm_nt(mgp_handle* h, int dtype, const void* P, int64_t ldp, int64_t m, const void* A, int64_t lda, int64_t n,
                 int64_t K, void* out, int64_t ldo, int accumulate, const int* gate) {
-  if (dtype == MGP_F64)
-    return gemm_nt_launch<double>(h, (const double*)P, ldp, m, (const double*)A, lda, n, K, (double*)out, ldo,
-                                  accumulate, gate);
-  return gemm_nt_launch<float>(h, (const float*)P, ldp, m, (const float*)A, lda, n, K, (float*)out, ldo, accumulate,
-                               gate);
+  return mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return gemm_nt_launch<T>(h, (const T*)P, ldp, m, (const T*)A, lda, n, K, (T*)out, ldo, accumulate, gate);
+  });
 }
 
 int mgp_mirror_upper(mgp_handle* h, int dtype, void* out, const void* slices, int nz, int64_t n, double scale) {
   const long tot = n * n;
-  if (dtype == MGP_F64)
-    hipLaunchKernelGGL((mirror_upper_kernel<double>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream,
-                       (double*)out, (const double*)slices, nz, n, scale);
-  else
-    hipLaunchKernelGGL((mirror_upper_kernel<float>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream,
-                       (float*)out, (const float*)slices, nz, n, (float)scale);
+  mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((mirror_upper_kernel<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, (T*)out,
+                       (const T*)slices, nz, n, (T)scale);
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
 }
@@ -1526,8 +1503,10 @@ int mgp_symm_matmul_gated(mgp_handle* h, int dtype, const void* A, int64_t n, co
   if (n < 0 || Bt < 0) return mgp_fail(h, MGP_E_SHAPE, "negative size");
   if (n == 0 || Bt == 0) return MGP_OK;
   if (!A || !P || !out) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
-  if (dtype == MGP_F64) return symm_matmul_t<double>(h, (const double*)A, n, (const double*)P, Bt, (double*)out, gate);
-  return symm_matmul_t<float>(h, (const float*)A, n, (const float*)P, Bt, (float*)out, gate);
+  return mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return symm_matmul_t<T>(h, (const T*)A, n, (const T*)P, Bt, (T*)out, gate);
+  });
 }
 
 extern "C" int mgp_symm_matmul(mgp_handle* h, int dtype, const void* A, int64_t n, const void* P, int64_t Bt,
@@ -1543,9 +1522,8 @@ extern "C" int mgp_k_dense(mgp_handle* h, const mgp_kernel* k, const void* A, in
   if (na == 0 || nb == 0) return MGP_OK;
   if (!A || !B || !out) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   if (k->D > MGP_FUSED_MAX_D) return mgp_k_dense_generic(h, k, A, na, B, nb, out, ld, jitter, diag_add, nullptr);
-  if (k->dtype == MGP_F64)
-    return k_dense_t<double>(h, k, (const double*)A, na, (const double*)B, nb, (double*)out, ld, jitter,
-                             (const double*)diag_add);
-  return k_dense_t<float>(h, k, (const float*)A, na, (const float*)B, nb, (float*)out, ld, jitter,
-                          (const float*)diag_add);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return k_dense_t<T>(h, k, (const T*)A, na, (const T*)B, nb, (T*)out, ld, jitter, (const T*)diag_add);
+  });
 }

@@ -111,16 +111,12 @@ int k_dense_generic_t(mgp_handle* h, const mgp_kernel* k, const T* A, long na, c
                       double jitter, const T* diag_add, const int* gate) {
   const double c = mgp_profile_scale(k->kind);
   dim3 grid((unsigned)((nb + GT - 1) / GT), (unsigned)((na + GT - 1) / GT));
-#define MGP_KG(KV)                                                                                              \
-  hipLaunchKernelGGL((k_dense_generic_kernel<T, KV>), grid, dim3(256), 0, h->stream, A, na, B, nb, out, ld, k->D, \
-                     (const double*)h->dparams, (T)k->variance, (T)(c * c * 1e-36), (T)jitter, diag_add, gate)
-  switch (k->kind) {
-    case MGP_SE: MGP_KG(0); break;
-    case MGP_MATERN12: MGP_KG(1); break;
-    case MGP_MATERN32: MGP_KG(2); break;
-    default: MGP_KG(3); break;
-  }
-#undef MGP_KG
+  mgp_with_kind(k->kind, [&](auto kind) {
+    hipLaunchKernelGGL((k_dense_generic_kernel<T, decltype(kind)::value>), grid, dim3(256), 0, h->stream, A, na, B, nb,
+                       out, ld, k->D, (const double*)h->dparams, (T)k->variance, (T)(c * c * 1e-36), (T)jitter,
+                       diag_add, gate);
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
 }
@@ -289,33 +285,6 @@ __global__ __launch_bounds__(256) void nearest_generic_kernel(const T* __restric
   }
 }
 
-// f = k/variance and f' = df/dr2 of the profile as functions of the PLAIN scaled squared distance
-// r2 = sum_d ((a_d - b_d) / l_d)^2 (grad.hip's formulas; GPflow's 1e-36 floor under the root)
-template <typename T, int KIND>
-__device__ __forceinline__ void profile_and_slope(T r2, T& f, T& fp) {
-  if (KIND == 0) {
-    f = mgp_exp2((T)(-0.5 * MGP_LOG2E) * r2);
-    fp = (T)-0.5 * f;
-  } else {
-    const bool floor_hit = !(r2 > (T)1e-36);
-    const T r = mgp_sqrt(floor_hit ? (T)1e-36 : r2);
-    if (KIND == 1) {
-      f = mgp_exp2((T)(-MGP_LOG2E) * r);
-      fp = floor_hit ? (T)0 : -f / ((T)2 * r);
-    } else if (KIND == 2) {
-      const T s3 = (T)1.7320508075688772935;
-      const T e = mgp_exp2((T)(-MGP_LOG2E) * s3 * r);
-      f = ((T)1 + s3 * r) * e;
-      fp = floor_hit ? (T)0 : (T)-1.5 * e;
-    } else {
-      const T s5 = (T)2.2360679774997896964;
-      const T e = mgp_exp2((T)(-MGP_LOG2E) * s5 * r);
-      f = ((T)1 + s5 * r + (T)(5.0 / 3.0) * r2) * e;
-      fp = floor_hit ? (T)0 : (T)(-5.0 / 6.0) * ((T)1 + s5 * r) * e;
-    }
-  }
-}
-
 // Kernel-block VJP at any D: part[blk][d] = sum over the block's pairs of G_ij f'(r2_ij) ((a_id - b_jd)/l_d)^2,
 // part[blk][D] = sum G_ij f_ij.  A workgroup takes one 64-column strip of a row range, tile by tile: first
 // pass over the dimensions -> r2 of its 4 x 4 pairs per thread (direct differences, as grad.hip), then
@@ -379,7 +348,7 @@ __global__ __launch_bounds__(256) void k_dense_vjp_generic_kernel(const T* __res
         T g = 0;
         if (i < ie && j < nb) g = G[i * ldg + j];
         T f, fp;
-        profile_and_slope<T, KIND>(r2[a][b], f, fp);
+        mgp_profile_slope<KIND>(r2[a][b], f, fp);
         gf += (double)(g * f);
         H[a][b] = g * fp;  // 0 outside the block: padded pairs contribute nothing
       }
@@ -413,9 +382,7 @@ __global__ __launch_bounds__(256) void k_dense_vjp_generic_kernel(const T* __res
       }
 #pragma unroll
       for (int d = 0; d < GK; ++d) {
-        double v = sd[d];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        const double v = mgp_wave_sum(sd[d]);
         if (lane == 0) red[wave][d] = v;
       }
       __syncthreads();
@@ -423,9 +390,7 @@ __global__ __launch_bounds__(256) void k_dense_vjp_generic_kernel(const T* __res
     }
   }
   {
-    double v = gf;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    const double v = mgp_wave_sum(gf);
     __syncthreads();
     if (lane == 0) red[wave][GK] = v;
     __syncthreads();
@@ -492,23 +457,16 @@ int nearest_generic_t(mgp_handle* h, const mgp_kernel* k, int dist_type, const T
     MGP_LAUNCH_CHECK(h);
   }
   dim3 grid((unsigned)((N + GT - 1) / GT));
-#define MGP_NG(KV, DV)                                                                                            \
-  hipLaunchKernelGGL((nearest_generic_kernel<T, KV, DV>), grid, dim3(256), 0, h->stream, X, N, Z, M, k->D,          \
-                     (const double*)h->dparams, (const T*)xn, (const T*)zn, (T)k->variance, (T)(c * c * 1e-36),   \
-                     dist_type, idx, best)
-#define MGP_NGK(KV)          \
-  do {                       \
-    if (direct) MGP_NG(KV, true); \
-    else MGP_NG(KV, false);  \
-  } while (0)
-  switch (k->kind) {
-    case MGP_SE: MGP_NGK(0); break;
-    case MGP_MATERN12: MGP_NGK(1); break;
-    case MGP_MATERN32: MGP_NGK(2); break;
-    default: MGP_NGK(3); break;
-  }
-#undef MGP_NGK
-#undef MGP_NG
+  mgp_with_kind(k->kind, [&](auto kind) {
+    auto launch = [&](auto dv) {
+      hipLaunchKernelGGL((nearest_generic_kernel<T, decltype(kind)::value, decltype(dv)::value>), grid, dim3(256), 0,
+                         h->stream, X, N, Z, M, k->D, (const double*)h->dparams, (const T*)xn, (const T*)zn,
+                         (T)k->variance, (T)(c * c * 1e-36), dist_type, idx, best);
+    };
+    if (direct) launch(std::true_type{});
+    else launch(std::false_type{});
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
 }
@@ -533,26 +491,13 @@ int vjp_generic_t(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const
   double* part = (double*)h->ws;
   dim3 grid((unsigned)nbx, (unsigned)nby);
   const size_t dyn = (size_t)(D + 1) * sizeof(double);
-#define MGP_VG(KV)                                                                                                   \
-  hipLaunchKernelGGL((k_dense_vjp_generic_kernel<T, KV>), grid, dim3(256), dyn, h->stream, A, na, B, nb, G, ldg, D, \
-                     (const double*)h->dparams, rows, part)
-  switch (k->kind) {
-    case MGP_SE: MGP_VG(0); break;
-    case MGP_MATERN12: MGP_VG(1); break;
-    case MGP_MATERN32: MGP_VG(2); break;
-    default: MGP_VG(3); break;
-  }
-#undef MGP_VG
+  mgp_with_kind(k->kind, [&](auto kind) {
+    hipLaunchKernelGGL((k_dense_vjp_generic_kernel<T, decltype(kind)::value>), grid, dim3(256), dyn, h->stream, A, na,
+                       B, nb, G, ldg, D, (const double*)h->dparams, rows, part);
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
-  std::vector<double> host((size_t)nblocks * (D + 1));
-  MGP_HIP(h, hipMemcpyAsync(host.data(), part, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  MGP_HIP(h, hipStreamSynchronize(h->stream));
-  std::vector<double> tot((size_t)D + 1, 0.0);
-  for (long bI = 0; bI < nblocks; ++bI)
-    for (int d = 0; d <= D; ++d) tot[(size_t)d] += host[(size_t)bI * (D + 1) + d];
-  *dvar = tot[(size_t)D];  // sum G f  == sum G k / variance
-  for (int d = 0; d < D; ++d) dls[d] = k->variance * (-2.0 / k->lengthscales[d]) * tot[(size_t)d];
-  return MGP_OK;
+  return mgp_fold_vjp_partials(h, part, nblocks, D + 1, k, dvar, dls);
 }
 
 template <typename T>
@@ -587,46 +532,43 @@ int sq_colsum_generic_t(mgp_handle* h, const mgp_kernel* k, const T* X, long N, 
 int mgp_k_dense_generic(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
                         void* out, int64_t ld, double jitter, const void* diag_add, const int* gate) {
   MGP_TRY(upload_scales(h, k));
-  if (k->dtype == MGP_F64)
-    return k_dense_generic_t<double>(h, k, (const double*)A, na, (const double*)B, nb, (double*)out, ld, jitter,
-                                     (const double*)diag_add, gate);
-  return k_dense_generic_t<float>(h, k, (const float*)A, na, (const float*)B, nb, (float*)out, ld, jitter,
-                                  (const float*)diag_add, gate);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return k_dense_generic_t<T>(h, k, (const T*)A, na, (const T*)B, nb, (T*)out, ld, jitter, (const T*)diag_add, gate);
+  });
 }
 
 int mgp_sweep_generic(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
                       VecView W, int32_t R, VecViewMut out, double alpha, VecView addend, const int* gate) {
   MGP_TRY(upload_scales(h, k));
-  if (k->dtype == MGP_F64)
-    return sweep_generic_t<double>(h, k, (const double*)A, na, (const double*)B, nb, (const double*)W.base, W.si,
-                                   W.sr, R, (double*)out.base, out.si, out.sr, alpha, (const double*)addend.base,
-                                   addend.si, addend.sr, gate);
-  return sweep_generic_t<float>(h, k, (const float*)A, na, (const float*)B, nb, (const float*)W.base, W.si, W.sr, R,
-                                (float*)out.base, out.si, out.sr, (float)alpha, (const float*)addend.base, addend.si,
-                                addend.sr, gate);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return sweep_generic_t<T>(h, k, (const T*)A, na, (const T*)B, nb, (const T*)W.base, W.si, W.sr, R, (T*)out.base,
+                              out.si, out.sr, (T)alpha, (const T*)addend.base, addend.si, addend.sr, gate);
+  });
 }
 
 int mgp_nearest_generic(mgp_handle* h, const mgp_kernel* k, int dist_type, const void* X, int64_t N, const void* Z,
                         int64_t M, int64_t* idx, void* best) {
-  if (k->dtype == MGP_F64)
-    return nearest_generic_t<double>(h, k, dist_type, (const double*)X, N, (const double*)Z, M, (long*)idx,
-                                     (double*)best);
-  return nearest_generic_t<float>(h, k, dist_type, (const float*)X, N, (const float*)Z, M, (long*)idx, (float*)best);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return nearest_generic_t<T>(h, k, dist_type, (const T*)X, N, (const T*)Z, M, (long*)idx, (T*)best);
+  });
 }
 
 int mgp_k_dense_vjp_generic(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
                             const void* G, int64_t ldg, double* dvariance, double* dlengthscales) {
-  if (k->dtype == MGP_F64)
-    return vjp_generic_t<double>(h, k, (const double*)A, na, (const double*)B, nb, (const double*)G, ldg, dvariance,
-                                 dlengthscales);
-  return vjp_generic_t<float>(h, k, (const float*)A, na, (const float*)B, nb, (const float*)G, ldg, dvariance,
-                              dlengthscales);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return vjp_generic_t<T>(h, k, (const T*)A, na, (const T*)B, nb, (const T*)G, ldg, dvariance, dlengthscales);
+  });
 }
 
 int mgp_kmn_sq_colsum_generic(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
                               void* out) {
   MGP_TRY(upload_scales(h, k));
-  if (k->dtype == MGP_F64)
-    return sq_colsum_generic_t<double>(h, k, (const double*)X, N, (const double*)Z, M, (double*)out);
-  return sq_colsum_generic_t<float>(h, k, (const float*)X, N, (const float*)Z, M, (float*)out);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return sq_colsum_generic_t<T>(h, k, (const T*)X, N, (const T*)Z, M, (T*)out);
+  });
 }

@@ -11,8 +11,6 @@
 // -(5/6)(1 + sqrt5 r) e^{-sqrt5 r}.  Direct differences are used for r2 (this is a gradient, the
 // expansion's cancellation error would be amplified).  Per-block partial sums are written out and
 // added on the host in block order: deterministic.
-#include <vector>
-
 #include "mgp_common.h"
 
 namespace {
@@ -61,27 +59,7 @@ __global__ __launch_bounds__(256) void k_dense_vjp_kernel(const T* __restrict__ 
         }
         const T g = G[(i0 + ii) * ldg + j];
         T f, fp;  // f = k/variance, fp = df/dr2
-        if (KIND == 0) {
-          f = mgp_exp2((T)(-0.5 * MGP_LOG2E) * r2);
-          fp = (T)-0.5 * f;
-        } else {
-          const bool floor_hit = !(r2 > (T)1e-36);
-          const T r = mgp_sqrt(floor_hit ? (T)1e-36 : r2);
-          if (KIND == 1) {
-            f = mgp_exp2((T)(-MGP_LOG2E) * r);
-            fp = floor_hit ? (T)0 : -f / ((T)2 * r);
-          } else if (KIND == 2) {
-            const T s3 = (T)1.7320508075688772935;
-            const T e = mgp_exp2((T)(-MGP_LOG2E) * s3 * r);
-            f = ((T)1 + s3 * r) * e;
-            fp = floor_hit ? (T)0 : (T)-1.5 * e;
-          } else {
-            const T s5 = (T)2.2360679774997896964;
-            const T e = mgp_exp2((T)(-MGP_LOG2E) * s5 * r);
-            f = ((T)1 + s5 * r + (T)(5.0 / 3.0) * r2) * e;
-            fp = floor_hit ? (T)0 : (T)(-5.0 / 6.0) * ((T)1 + s5 * r) * e;
-          }
-        }
+        mgp_profile_slope<KIND>(r2, f, fp);
         acc[DP] += (double)(g * f);
         const T gfp = g * fp;
 #pragma unroll
@@ -95,7 +73,7 @@ __global__ __launch_bounds__(256) void k_dense_vjp_kernel(const T* __restrict__ 
   for (int d = 0; d <= DP; ++d) {
     double v = acc[d];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);  // mgp_wave_sum, spelled out: see DESIGN 4.0
     if (lane == 0) red[wave][d] = v;
   }
   __syncthreads();
@@ -105,13 +83,12 @@ __global__ __launch_bounds__(256) void k_dense_vjp_kernel(const T* __restrict__ 
   }
 }
 
-template <typename T, int KIND>
-int vjp_dp(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const T* B, long nb, const T* G, long ldg,
-           double* dvar, double* dls) {
+template <typename T>
+int vjp_t(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const T* B, long nb, const T* G, long ldg,
+          double* dvar, double* dls) {
   SweepParams prm = mgp_make_params(k);
   for (int d = 0; d < MGP_FUSED_MAX_D; ++d) prm.inv_ls[d] = d < k->D ? 1.0 / k->lengthscales[d] : 0.0;
   const int D = k->D;
-  const int DPv = D <= 2 ? 2 : (D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)));
   const long nbx = (nb + 255) / 256;
   long nby = (4L * h->num_cus + nbx - 1) / nbx;
   const long max_y = (na + 31) / 32;
@@ -121,41 +98,18 @@ int vjp_dp(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const T* B, 
   rows = (rows + 31) / 32 * 32;
   nby = (na + rows - 1) / rows;
   const long nblocks = nbx * nby;
-  MGP_TRY(mgp_reserve(h, &h->ws, &h->ws_bytes, (size_t)nblocks * (DPv + 1) * sizeof(double)));
-  double* part = (double*)h->ws;
   dim3 grid((unsigned)nbx, (unsigned)nby);
-#define MGP_VJP(DPV) \
-  hipLaunchKernelGGL((k_dense_vjp_kernel<T, DPV, KIND>), grid, dim3(256), 0, h->stream, A, na, B, nb, G, ldg, D, prm, \
-                     rows, part)
-  switch (DPv) {
-    case 2: MGP_VJP(2); break;
-    case 4: MGP_VJP(4); break;
-    case 8: MGP_VJP(8); break;
-    case 16: MGP_VJP(16); break;
-    default: MGP_VJP(32); break;
-  }
-#undef MGP_VJP
-  MGP_LAUNCH_CHECK(h);
-  std::vector<double> host((size_t)nblocks * (DPv + 1));
-  MGP_HIP(h, hipMemcpyAsync(host.data(), part, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  MGP_HIP(h, hipStreamSynchronize(h->stream));
-  std::vector<double> tot(DPv + 1, 0.0);
-  for (long bI = 0; bI < nblocks; ++bI)
-    for (int d = 0; d <= DPv; ++d) tot[d] += host[(size_t)bI * (DPv + 1) + d];
-  *dvar = tot[DPv];  // sum G f  == sum G k / variance
-  for (int d = 0; d < D; ++d) dls[d] = k->variance * (-2.0 / k->lengthscales[d]) * tot[d];
-  return MGP_OK;
-}
-
-template <typename T>
-int vjp_t(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const T* B, long nb, const T* G, long ldg,
-          double* dvar, double* dls) {
-  switch (k->kind) {
-    case MGP_SE: return vjp_dp<T, 0>(h, k, A, na, B, nb, G, ldg, dvar, dls);
-    case MGP_MATERN12: return vjp_dp<T, 1>(h, k, A, na, B, nb, G, ldg, dvar, dls);
-    case MGP_MATERN32: return vjp_dp<T, 2>(h, k, A, na, B, nb, G, ldg, dvar, dls);
-    default: return vjp_dp<T, 3>(h, k, A, na, B, nb, G, ldg, dvar, dls);
-  }
+  return mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp(D, [&](auto dp) {
+      constexpr int DP = decltype(dp)::value;
+      MGP_TRY(mgp_reserve(h, &h->ws, &h->ws_bytes, (size_t)nblocks * (DP + 1) * sizeof(double)));
+      double* part = (double*)h->ws;
+      hipLaunchKernelGGL((k_dense_vjp_kernel<T, DP, decltype(kind)::value>), grid, dim3(256), 0, h->stream, A, na, B,
+                         nb, G, ldg, D, prm, rows, part);
+      MGP_LAUNCH_CHECK(h);
+      return mgp_fold_vjp_partials(h, part, nblocks, DP + 1, k, dvar, dls);
+    });
+  });
 }
 
 }  // namespace
@@ -171,9 +125,8 @@ extern "C" int mgp_k_dense_vjp(mgp_handle* h, const mgp_kernel* k, const void* A
   if (!A || !B || !G) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   if (k->D > MGP_FUSED_MAX_D)  // generic.hip: dimensions staged through LDS
     return mgp_k_dense_vjp_generic(h, k, A, na, B, nb, G, ldg, dvariance, dlengthscales);
-  if (k->dtype == MGP_F64)
-    return vjp_t<double>(h, k, (const double*)A, na, (const double*)B, nb, (const double*)G, ldg, dvariance,
-                         dlengthscales);
-  return vjp_t<float>(h, k, (const float*)A, na, (const float*)B, nb, (const float*)G, ldg, dvariance,
-                      dlengthscales);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return vjp_t<T>(h, k, (const T*)A, na, (const T*)B, nb, (const T*)G, ldg, dvariance, dlengthscales);
+  });
 }

@@ -19,6 +19,17 @@ void mgp_host_profile(int kind, const double* s, double* out, long n) {
     }
   }
 }
+// f = k/variance and fp = df/dr2 at the plain scaled squared distance r2 (mgp_profile_slope, the gradients' form)
+void mgp_host_profile_slope(int kind, const double* r2, double* f, double* fp, long n) {
+  for (long i = 0; i < n; ++i) {
+    switch (kind) {
+      case 0: mgp_profile_slope<0>(r2[i], f[i], fp[i]); break;
+      case 1: mgp_profile_slope<1>(r2[i], f[i], fp[i]); break;
+      case 2: mgp_profile_slope<2>(r2[i], f[i], fp[i]); break;
+      default: mgp_profile_slope<3>(r2[i], f[i], fp[i]); break;
+    }
+  }
+}
 double mgp_host_profile_scale(int kind) { return mgp_profile_scale(kind); }
 // out[i] = 2^(s[i] - a2[i]) through the shifted table form, including the per-point 2^rho
 void mgp_host_exp2_shifted(const double* s, const double* a2, double* out, long n) {

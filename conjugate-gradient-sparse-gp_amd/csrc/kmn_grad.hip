@@ -31,32 +31,6 @@ namespace {
 constexpr int kVjpThreads = 256;  // columns per workgroup of the pair kernel
 constexpr int kVjpTR = 32;        // rows staged per LDS tile
 
-// f = k / variance and fp = df/dr2 at the scaled squared distance r2 (grad.hip's forms)
-template <int KIND>
-__device__ __forceinline__ void kvjp_profile(double r2, double& f, double& fp) {
-  if (KIND == 0) {
-    f = mgp_exp2(-0.5 * MGP_LOG2E * r2);
-    fp = -0.5 * f;
-  } else {
-    const bool floor_hit = !(r2 > 1e-36);
-    const double r = mgp_sqrt(floor_hit ? 1e-36 : r2);
-    if (KIND == 1) {
-      f = mgp_exp2(-MGP_LOG2E * r);
-      fp = floor_hit ? 0.0 : -f / (2.0 * r);
-    } else if (KIND == 2) {
-      const double s3 = 1.7320508075688772935;
-      const double e = mgp_exp2(-MGP_LOG2E * s3 * r);
-      f = mgp_fma(s3, r, 1.0) * e;
-      fp = floor_hit ? 0.0 : -1.5 * e;
-    } else {
-      const double s5 = 2.2360679774997896964;
-      const double e = mgp_exp2(-MGP_LOG2E * s5 * r);
-      f = mgp_fma(5.0 / 3.0, r2, mgp_fma(s5, r, 1.0)) * e;
-      fp = floor_hit ? 0.0 : (-5.0 / 6.0) * mgp_fma(s5, r, 1.0) * e;
-    }
-  }
-}
-
 // G2 = Gq + Gq^T (G2[i, j] and G2[j, i] are the same two addends: exactly symmetric)
 __global__ __launch_bounds__(256) void kvjp_sym_kernel(const double* __restrict__ Gq, long M, double* __restrict__ G2) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -95,7 +69,7 @@ __global__ __launch_bounds__(kVjpThreads) void kvjp_kpanel_kernel(const double* 
       r2 = mgp_fma(df, df, r2);
     }
     double f, fp;
-    kvjp_profile<KIND>(r2, f, fp);
+    mgp_profile_slope<KIND>(r2, f, fp);
     Kp[(i0 + ii) * M + m] = prm.variance * f;
   }
 }
@@ -145,7 +119,7 @@ __global__ __launch_bounds__(kVjpThreads) void kvjp_pairs_kernel(const double* _
           r2 = mgp_fma(df, df, r2);
         }
         double f, fp;
-        kvjp_profile<KIND>(r2, f, fp);
+        mgp_profile_slope<KIND>(r2, f, fp);
         accv = mgp_fma(w, f, accv);
         const double g = w * fp;
 #pragma unroll
@@ -167,9 +141,7 @@ __global__ __launch_bounds__(kVjpThreads) void kvjp_pairs_kernel(const double* _
   const int lane = t & 63, wave = t >> 6;
 #pragma unroll
   for (int d = 0; d <= DP; ++d) {
-    double v = d < DP ? accl[d] : accv;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    const double v = mgp_wave_sum(d < DP ? accl[d] : accv);
     if (lane == 0) red[wave][d] = v;
   }
   __syncthreads();
@@ -283,16 +255,6 @@ int kvjp_run(mgp_handle* h, const mgp_kernel* k, const double* X, long N, const 
   return MGP_OK;
 }
 
-template <int KIND>
-int kvjp_kind(mgp_handle* h, const mgp_kernel* k, const double* X, long N, const double* Z, long M, const double* Gq,
-              const double* Y, const double* Gb, int P, double* dvar, double* dls, double* dZ) {
-  const int D = k->D;
-  if (D <= 4) return kvjp_run<4, KIND>(h, k, X, N, Z, M, Gq, Y, Gb, P, dvar, dls, dZ);
-  if (D <= 8) return kvjp_run<8, KIND>(h, k, X, N, Z, M, Gq, Y, Gb, P, dvar, dls, dZ);
-  if (D <= 16) return kvjp_run<16, KIND>(h, k, X, N, Z, M, Gq, Y, Gb, P, dvar, dls, dZ);
-  return kvjp_run<32, KIND>(h, k, X, N, Z, M, Gq, Y, Gb, P, dvar, dls, dZ);
-}
-
 }  // namespace
 
 extern "C" int mgp_kmn_knm_vjp(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
@@ -318,10 +280,10 @@ extern "C" int mgp_kmn_knm_vjp(mgp_handle* h, const mgp_kernel* k, const void* X
   const double *Xd = (const double*)X, *Zd = (const double*)Z, *Gqd = (const double*)Gq;
   const double *Yd = P > 0 ? (const double*)Y : nullptr, *Gbd = P > 0 ? (const double*)Gb : nullptr;
   double* dZd = (double*)dZ;
-  switch (k->kind) {
-    case MGP_SE: return kvjp_kind<0>(h, k, Xd, N, Zd, M, Gqd, Yd, Gbd, P, dvariance, dlengthscales, dZd);
-    case MGP_MATERN12: return kvjp_kind<1>(h, k, Xd, N, Zd, M, Gqd, Yd, Gbd, P, dvariance, dlengthscales, dZd);
-    case MGP_MATERN32: return kvjp_kind<2>(h, k, Xd, N, Zd, M, Gqd, Yd, Gbd, P, dvariance, dlengthscales, dZd);
-    default: return kvjp_kind<3>(h, k, Xd, N, Zd, M, Gqd, Yd, Gbd, P, dvariance, dlengthscales, dZd);
-  }
+  return mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp<4>(k->D, [&](auto dp) {
+      return kvjp_run<decltype(dp)::value, decltype(kind)::value>(h, k, Xd, N, Zd, M, Gqd, Yd, Gbd, P, dvariance,
+                                                                  dlengthscales, dZd);
+    });
+  });
 }

@@ -436,16 +436,6 @@ int kxx_dp(mgp_handle* h, const mgp_kernel* k, const double* X, long N, double s
   return MGP_OK;
 }
 
-template <int KIND>
-int kxx_kind(mgp_handle* h, const mgp_kernel* k, const double* X, long N, double s2, VecView V, int R, VecViewMut out,
-             const int* gate) {
-  const int D = k->D;
-  if (D <= 4) return kxx_dp<4, KIND>(h, k, X, N, s2, V, R, out, gate);
-  if (D <= 8) return kxx_dp<8, KIND>(h, k, X, N, s2, V, R, out, gate);
-  if (D <= 16) return kxx_dp<16, KIND>(h, k, X, N, s2, V, R, out, gate);
-  return kxx_dp<32, KIND>(h, k, X, N, s2, V, R, out, gate);
-}
-
 }  // namespace
 
 // Dispatch (measured): the symmetric form serves ONE right-hand side, fp64, D <= MGP_FUSED_MAX_D, from
@@ -464,12 +454,11 @@ int mgp_kxx(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double
                    (h->kxx_mode == 1 || (h->kxx_mode == 0 && R == 1 && N >= h->kxx_min_n));
   if (!sym) return mgp_sweep(h, k, X, N, X, N, V, R, out, s2, V, gate);
   const double* Xd = (const double*)X;
-  switch (k->kind) {
-    case MGP_SE: return kxx_kind<0>(h, k, Xd, N, s2, V, R, out, gate);
-    case MGP_MATERN12: return kxx_kind<1>(h, k, Xd, N, s2, V, R, out, gate);
-    case MGP_MATERN32: return kxx_kind<2>(h, k, Xd, N, s2, V, R, out, gate);
-    default: return kxx_kind<3>(h, k, Xd, N, s2, V, R, out, gate);
-  }
+  return mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp<4>(k->D, [&](auto dp) {
+      return kxx_dp<decltype(dp)::value, decltype(kind)::value>(h, k, Xd, N, s2, V, R, out, gate);
+    });
+  });
 }
 
 extern "C" int mgp_kxx_matvec(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, const void* V,

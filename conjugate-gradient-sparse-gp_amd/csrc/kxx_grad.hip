@@ -54,32 +54,6 @@ __global__ __launch_bounds__(256) void kgrad_pack_uv_kernel(const T* __restrict_
   UV[e] = w;
 }
 
-// f = k / variance and fp = df/dr2 at the scaled squared distance r2 (grad.hip's forms)
-template <int KIND>
-__device__ __forceinline__ void kgrad_profile(double r2, double& f, double& fp) {
-  if (KIND == 0) {
-    f = mgp_exp2(-0.5 * MGP_LOG2E * r2);
-    fp = -0.5 * f;
-  } else {
-    const bool floor_hit = !(r2 > 1e-36);
-    const double r = mgp_sqrt(floor_hit ? 1e-36 : r2);
-    if (KIND == 1) {
-      f = mgp_exp2(-MGP_LOG2E * r);
-      fp = floor_hit ? 0.0 : -f / (2.0 * r);
-    } else if (KIND == 2) {
-      const double s3 = 1.7320508075688772935;
-      const double e = mgp_exp2(-MGP_LOG2E * s3 * r);
-      f = mgp_fma(s3, r, 1.0) * e;
-      fp = floor_hit ? 0.0 : -1.5 * e;
-    } else {
-      const double s5 = 2.2360679774997896964;
-      const double e = mgp_exp2(-MGP_LOG2E * s5 * r);
-      f = mgp_fma(5.0 / 3.0, r2, mgp_fma(s5, r, 1.0)) * e;
-      fp = floor_hit ? 0.0 : (-5.0 / 6.0) * mgp_fma(s5, r, 1.0) * e;
-    }
-  }
-}
-
 template <int DP, int KIND, int RC>
 __global__ __launch_bounds__(kKgThreads) void kxx_grad_kernel(const double* __restrict__ P,
                                                               const double* __restrict__ UV, long nbk, long ntiles,
@@ -126,7 +100,7 @@ __global__ __launch_bounds__(kKgThreads) void kxx_grad_kernel(const double* __re
       }
       __builtin_amdgcn_sched_barrier(0);
       double f, fp;
-      kgrad_profile<KIND>(r2, f, fp);
+      mgp_profile_slope<KIND>(r2, f, fp);
       acc[DP] = mgp_fma(c, f, acc[DP]);
       const double g = c * fp;
 #pragma unroll
@@ -139,9 +113,7 @@ __global__ __launch_bounds__(kKgThreads) void kxx_grad_kernel(const double* __re
   const int lane = t & 63, wave = t >> 6;
 #pragma unroll
   for (int d = 0; d <= DP; ++d) {
-    double v = acc[d];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    const double v = mgp_wave_sum(acc[d]);
     if (lane == 0) red[wave][d] = v;
   }
   __syncthreads();
@@ -179,7 +151,7 @@ int kgrad_fused(mgp_handle* h, const mgp_kernel* k, const T* X, long N, VecView 
   hipLaunchKernelGGL((kgrad_pack_x_kernel<T, DP>), dim3((unsigned)((npad * DP + 255) / 256)), dim3(256), 0, h->stream,
                      X, N, npad, k->D, prm, P);
   MGP_LAUNCH_CHECK(h);
-  std::vector<double> host((size_t)grid * (DP + 1)), tot(DP + 1, 0.0);
+  double tot[DP + 1] = {0.0};  // running sums over the groups' blocks
   int r0 = 0;
   while (r0 < R) {
     const int left = R - r0;
@@ -194,25 +166,10 @@ int kgrad_fused(mgp_handle* h, const mgp_kernel* k, const T* X, long N, VecView 
       case 2: MGP_TRY((kgrad_pass<DP, KIND, 2>(h, P, UV, nbk, ntiles, grid, part))); break;
       default: MGP_TRY((kgrad_pass<DP, KIND, 1>(h, P, UV, nbk, ntiles, grid, part))); break;
     }
-    MGP_HIP(h, hipMemcpyAsync(host.data(), part, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    MGP_HIP(h, hipStreamSynchronize(h->stream));
-    for (long b = 0; b < grid; ++b)
-      for (int d = 0; d <= DP; ++d) tot[d] += host[(size_t)b * (DP + 1) + d];
+    MGP_TRY(mgp_fold_vjp_partials(h, part, grid, DP + 1, k, dvar, dls, tot));
     r0 += rc;
   }
-  *dvar = tot[DP];
-  for (int d = 0; d < k->D; ++d) dls[d] = k->variance * (-2.0 / k->lengthscales[d]) * tot[d];
   return MGP_OK;
-}
-
-template <typename T, int KIND>
-int kgrad_kind(mgp_handle* h, const mgp_kernel* k, const T* X, long N, VecView U, VecView V, int R, double* dvar,
-               double* dls) {
-  const int D = k->D;
-  if (D <= 4) return kgrad_fused<T, 4, KIND>(h, k, X, N, U, V, R, dvar, dls);
-  if (D <= 8) return kgrad_fused<T, 8, KIND>(h, k, X, N, U, V, R, dvar, dls);
-  if (D <= 16) return kgrad_fused<T, 16, KIND>(h, k, X, N, U, V, R, dvar, dls);
-  return kgrad_fused<T, 32, KIND>(h, k, X, N, U, V, R, dvar, dls);
 }
 
 // G[ii, j] = sum_r U(i0 + ii, r) V(j, r) for a panel of rows
@@ -272,13 +229,15 @@ extern "C" int mgp_kxx_grad(mgp_handle* h, const mgp_kernel* k, const void* X, i
   if (k->dtype == MGP_F64 && k->D <= MGP_FUSED_MAX_D && h->kxx_grad_mode != 2) {
     if ((N + kKgTB - 1) / kKgTB > 2147483647L / 2) return mgp_fail(h, MGP_E_SHAPE, "kxx_grad: N too large");
     const double* Xd = (const double*)X;
-    switch (k->kind) {
-      case MGP_SE: return kgrad_kind<double, 0>(h, k, Xd, N, Uv, Vv, R, dvariance, dlengthscales);
-      case MGP_MATERN12: return kgrad_kind<double, 1>(h, k, Xd, N, Uv, Vv, R, dvariance, dlengthscales);
-      case MGP_MATERN32: return kgrad_kind<double, 2>(h, k, Xd, N, Uv, Vv, R, dvariance, dlengthscales);
-      default: return kgrad_kind<double, 3>(h, k, Xd, N, Uv, Vv, R, dvariance, dlengthscales);
-    }
+    return mgp_with_kind(k->kind, [&](auto kind) {
+      return mgp_with_dp<4>(k->D, [&](auto dp) {
+        return kgrad_fused<double, decltype(dp)::value, decltype(kind)::value>(h, k, Xd, N, Uv, Vv, R, dvariance,
+                                                                               dlengthscales);
+      });
+    });
   }
-  if (k->dtype == MGP_F64) return kgrad_panel<double>(h, k, (const double*)X, N, Uv, Vv, R, dvariance, dlengthscales);
-  return kgrad_panel<float>(h, k, (const float*)X, N, Uv, Vv, R, dvariance, dlengthscales);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return kgrad_panel<T>(h, k, (const T*)X, N, Uv, Vv, R, dvariance, dlengthscales);
+  });
 }

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -270,6 +271,44 @@ __device__ __forceinline__ float mgp_read_lane(float v, int src) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
+// sum over the 64 lanes of a wave, the result in every lane: xor butterfly, offsets 32 .. 1
+template <typename T>
+__device__ __forceinline__ T mgp_wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// Run-time kernel kind, input dimension and dtype as compile-time constants of a generic lambda: the one place
+// where the kind switch and the padded-dimension ladder are written.  f receives std::integral_constant<int, V>
+// (read as decltype(arg)::value) or a value of the element type, and returns the entry point's int.
+template <typename F>
+inline int mgp_with_kind(int kind, F&& f) {
+  switch (kind) {
+    case MGP_SE: return f(std::integral_constant<int, 0>{});
+    case MGP_MATERN12: return f(std::integral_constant<int, 1>{});
+    case MGP_MATERN32: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
+  }
+}
+// DP = the smallest of {2, 4, 8, 16, 32} that is >= max(D, MIN_DP); paddings below MIN_DP are not instantiated
+template <int MIN_DP = 2, typename F>
+inline int mgp_with_dp(int D, F&& f) {
+  if constexpr (MIN_DP <= 2)
+    if (D <= 2) return f(std::integral_constant<int, 2>{});
+  if constexpr (MIN_DP <= 4)
+    if (D <= 4) return f(std::integral_constant<int, 4>{});
+  if constexpr (MIN_DP <= 8)
+    if (D <= 8) return f(std::integral_constant<int, 8>{});
+  if constexpr (MIN_DP <= 16)
+    if (D <= 16) return f(std::integral_constant<int, 16>{});
+  return f(std::integral_constant<int, 32>{});
+}
+template <typename F>
+inline int mgp_with_dtype(int dtype, F&& f) {
+  return dtype == MGP_F64 ? f(double{}) : f(float{});
+}
+
 int mgp_build_e2tabs(mgp_handle* h);  // sweep.hip
 // dense.hip: slots Q[nt][n] (h->ws) and the (I, J) table of the one-RHS upper-triangle product, nt = ceil(n/64);
 // Q[k][i] = contribution of chunk k to output element i, summed by the caller in k order
@@ -389,3 +428,22 @@ int mgp_symm_matmul_gated(mgp_handle* h, int dtype, const void* A, int64_t n, co
 // pivchol.hip: Z[Bt, n] = diag_inv o R - (R B^T) B, B [k, n]; gate: device int, skip if 0
 int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
                             const void* R, int64_t Bt, void* Z, const int* gate);
+
+// Host tail of a kernel-block VJP.  part [nblocks][width] on the device holds per-workgroup sums: width - 1
+// lengthscale sums (the first k->D count), then the variance sum.  They are copied to the host and added in block
+// order (deterministic), then *dvar = tot[width - 1] and dls[d] = variance (-2 / l_d) tot[d].  carry [width], when
+// given, holds the running sums: they continue from it and are left in it, so a caller that launches in several
+// groups (kxx_grad.hip's right-hand-side groups) gets one sum over all blocks of all groups, scaled once.
+// Synchronises the stream.
+inline int mgp_fold_vjp_partials(mgp_handle* h, const double* part, long nblocks, int width, const mgp_kernel* k,
+                                 double* dvar, double* dls, double* carry = nullptr) {
+  std::vector<double> host((size_t)nblocks * width), own(carry ? 0 : width, 0.0);
+  MGP_HIP(h, hipMemcpyAsync(host.data(), part, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  MGP_HIP(h, hipStreamSynchronize(h->stream));
+  double* tot = carry ? carry : own.data();
+  for (long b = 0; b < nblocks; ++b)
+    for (int d = 0; d < width; ++d) tot[d] += host[(size_t)b * width + d];
+  *dvar = tot[width - 1];  // sum G f == sum G k / variance
+  for (int d = 0; d < k->D; ++d) dls[d] = k->variance * (-2.0 / k->lengthscales[d]) * tot[d];
+  return MGP_OK;
+}

@@ -183,3 +183,40 @@ MGP_HD T mgp_profile(T neg_s, T clamp, E2 e2 = E2()) {
     return mgp_fma(mgp_fma(q, c2, (T)MGP_LN2), q, (T)1.0) * e;
   }
 }
+
+// f = k / variance and fp = df/dr2 as functions of the PLAIN scaled squared distance r2 = sum_d ((a_d - b_d) / l_d)^2:
+// the one form behind every gradient and every direct-difference kernel value (grad.hip, generic.hip, kxx_grad.hip,
+// kmn_grad.hip, pivchol.hip).  Inputs are scaled by 1 / l only (no profile scale c_kind), and callers form r2 from
+// direct differences: a gradient amplifies the cancellation of the expansion form.  GPflow's floor under the square
+// root, r = sqrt(max(r2, 1e-36)), is kept; at the floor max() picks the constant, so the Matern slopes are exactly 0
+// there (Matern-1/2 would divide by r otherwise: coincident points add nothing and never a NaN).  A NaN r2 stays NaN
+// through the SE form; the Matern forms take the floor for it (the comparison is false), value and slope alike.
+//   SE        f = e^{-r2/2}                                   f' = -f/2
+//   Matern12  f = e^{-r}                                      f' = -f/(2r)
+//   Matern32  f = (1 + sqrt3 r) e^{-sqrt3 r}                  f' = -(3/2) e^{-sqrt3 r}
+//   Matern52  f = (1 + sqrt5 r + 5 r2/3) e^{-sqrt5 r}         f' = -(5/6)(1 + sqrt5 r) e^{-sqrt5 r}
+template <int KIND, typename T>
+MGP_HD void mgp_profile_slope(T r2, T& f, T& fp) {
+  if (KIND == 0) {
+    f = mgp_exp2((T)(-0.5 * MGP_LOG2E) * r2);
+    fp = (T)-0.5 * f;
+  } else {
+    const T rc = r2 > (T)1e-36 ? r2 : (T)1e-36;  // tf.maximum(r2, 1e-36)
+    const bool floor_hit = !(rc > (T)1e-36);
+    const T r = mgp_sqrt(rc);
+    if (KIND == 1) {
+      f = mgp_exp2((T)(-MGP_LOG2E) * r);
+      fp = floor_hit ? (T)0 : -f / ((T)2 * r);
+    } else if (KIND == 2) {
+      const T s3 = (T)1.7320508075688772935;
+      const T e = mgp_exp2((T)(-MGP_LOG2E) * s3 * r);
+      f = mgp_fma(s3, r, (T)1) * e;
+      fp = floor_hit ? (T)0 : (T)-1.5 * e;
+    } else {
+      const T s5 = (T)2.2360679774997896964;
+      const T e = mgp_exp2((T)(-MGP_LOG2E) * s5 * r);
+      f = mgp_fma((T)(5.0 / 3.0), r2, mgp_fma(s5, r, (T)1)) * e;
+      fp = floor_hit ? (T)0 : (T)(-5.0 / 6.0) * mgp_fma(s5, r, (T)1) * e;
+    }
+  }
+}

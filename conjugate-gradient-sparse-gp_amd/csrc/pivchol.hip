@@ -63,21 +63,6 @@ __device__ __forceinline__ PcTriple pc_block_reduce(PcTriple v, double* smx, lon
   return r;
 }
 
-// k(x_p, x_c) / variance from direct differences of the rows scaled by 1 / lengthscale (the forms of grad.hip:
-// GPflow's K_r2 / K_r with its 1e-36 floor under the square root)
-template <int KIND>
-__device__ __forceinline__ double pc_profile(double r2) {
-  if (KIND == 0) return mgp_exp2(-0.5 * MGP_LOG2E * r2);
-  const double r = mgp_sqrt(r2 > 1e-36 ? r2 : 1e-36);
-  if (KIND == 1) return mgp_exp2(-MGP_LOG2E * r);
-  if (KIND == 2) {
-    const double s3 = 1.7320508075688772935;
-    return (1.0 + s3 * r) * mgp_exp2(-MGP_LOG2E * s3 * r);
-  }
-  const double s5 = 2.2360679774997896964;
-  return (1.0 + s5 * r + (5.0 / 3.0) * r2) * mgp_exp2(-MGP_LOG2E * s5 * r);
-}
-
 // d = variance everywhere, the partials of step 0, the state word
 __global__ __launch_bounds__(PC_NT) void pivchol_init_kernel(double* __restrict__ d, long N, long slice, double variance,
                                                               double* __restrict__ pmx, long* __restrict__ pix,
@@ -164,7 +149,10 @@ __global__ __launch_bounds__(PC_NT) void pivchol_step_kernel(const double* __res
         const double df = xc[e] * sinv[e] - xp[e];
         r2 = mgp_fma(df, df, r2);
       }
-      double acc = variance * pc_profile<KIND>(r2);
+      // k(x_p, x_c) / variance from direct differences of the rows scaled by 1 / lengthscale; the slope is not used
+      double f, fp;
+      mgp_profile_slope<KIND>(r2, f, fp);
+      double acc = variance * f;
 #pragma unroll 8
       for (int j = 0; j < i; ++j) acc = mgp_fma(-lp[j], L[(long)j * N + c], acc);
       lv = acc * inv_root;
@@ -219,9 +207,7 @@ __global__ __launch_bounds__(256) void lowrank_dot_kernel(const int* __restrict_
     }
 #pragma unroll
     for (int b = 0; b < BT; ++b) {
-      T v = acc[b];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      const T v = mgp_wave_sum(acc[b]);
       if (lane == 0 && b < bt) part[((long)blockIdx.x * bt + b) * k + i] = v;
     }
   }
@@ -320,10 +306,10 @@ int lowrank_apply_t(mgp_handle* h, const T* dinv, const T* B, long k, long n, co
 // internal: the gated form the CG loop enqueues (steps past convergence do nothing)
 int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
                             const void* R, int64_t Bt, void* Z, const int* gate) {
-  if (dtype == MGP_F64)
-    return lowrank_apply_t<double>(h, (const double*)diag_inv, (const double*)B, k, n, (const double*)R, Bt, (double*)Z,
-                                   gate);
-  return lowrank_apply_t<float>(h, (const float*)diag_inv, (const float*)B, k, n, (const float*)R, Bt, (float*)Z, gate);
+  return mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return lowrank_apply_t<T>(h, (const T*)diag_inv, (const T*)B, k, n, (const T*)R, Bt, (T*)Z, gate);
+  });
 }
 
 extern "C" int mgp_lowrank_apply(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
@@ -376,17 +362,13 @@ extern "C" int mgp_kxx_pivchol(mgp_handle* h, const mgp_kernel* k, const void* X
   const double stop_sum = rel_tol * (double)N * k->variance;
   for (int i = 0; i < kmax; ++i) {
     const int a = i & 1, b = a ^ 1;
-#define MGP_PC(KV)                                                                                                   \
-  hipLaunchKernelGGL((pivchol_step_kernel<KV>), dim3((unsigned)G), dim3(PC_NT), 0, s, (const double*)X, (long)N, k->D, \
-                     (const double*)inv_ls, k->variance, stop_sum, i, (double*)L, d, (long*)piv, slice,                \
-                     (const double*)pmx[a], (const long*)pix[a], (const double*)psm[a], pmx[b], pix[b], psm[b], st)
-    switch (k->kind) {
-      case MGP_SE: MGP_PC(0); break;
-      case MGP_MATERN12: MGP_PC(1); break;
-      case MGP_MATERN32: MGP_PC(2); break;
-      default: MGP_PC(3); break;
-    }
-#undef MGP_PC
+    MGP_TRY(mgp_with_kind(k->kind, [&](auto kind) {
+      hipLaunchKernelGGL((pivchol_step_kernel<decltype(kind)::value>), dim3((unsigned)G), dim3(PC_NT), 0, s,
+                         (const double*)X, (long)N, k->D, (const double*)inv_ls, k->variance, stop_sum, i, (double*)L, d,
+                         (long*)piv, slice, (const double*)pmx[a], (const long*)pix[a], (const double*)psm[a], pmx[b],
+                         pix[b], psm[b], st);
+      return MGP_OK;
+    }));
     MGP_LAUNCH_CHECK(h);
   }
   if (diag) MGP_HIP(h, hipMemcpyAsync(diag, d, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, s));

@@ -195,13 +195,6 @@ __global__ __launch_bounds__(256) void knm_project_kernel(const double* __restri
     }
 }
 
-template <typename T>
-__device__ __forceinline__ T pj_wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // one wave per test row: proj[b, j] = variance * sum_split part (split order), sqnorm[b] = sum_j proj[b, j]^2
 __global__ __launch_bounds__(256) void knm_project_reduce_kernel(const double* __restrict__ part, int nsplit, long Bpad,
                                                                  int RP, long B, int r, double variance,
@@ -218,7 +211,7 @@ __global__ __launch_bounds__(256) void knm_project_reduce_kernel(const double* _
     if (proj != nullptr) proj[b * r + j] = s;
     sq = mgp_fma(s, s, sq);
   }
-  sq = pj_wave_sum(sq);
+  sq = mgp_wave_sum(sq);
   if (lane == 0 && sqnorm != nullptr) sqnorm[b] = sq;
 }
 
@@ -243,7 +236,7 @@ __global__ __launch_bounds__(256) void pj_row_sqsum_kernel(const T* __restrict__
     const T v = P[b * r + j];
     sq = mgp_fma(v, v, sq);
   }
-  sq = pj_wave_sum(sq);
+  sq = mgp_wave_sum(sq);
   if (lane == 0) sqnorm[b] = sq;
 }
 
@@ -305,17 +298,6 @@ int project_fused_dp(mgp_handle* h, const mgp_kernel* k, const double* Xs, long 
   return MGP_OK;
 }
 
-template <int KIND>
-int project_fused(mgp_handle* h, const mgp_kernel* k, const double* Xs, long B, const double* X, long N,
-                  const double* R, int r, int r_layout, double* proj, double* sqnorm) {
-  const int D = k->D;
-  if (D <= 2) return project_fused_dp<KIND, 2>(h, k, Xs, B, X, N, R, r, r_layout, proj, sqnorm);
-  if (D <= 4) return project_fused_dp<KIND, 4>(h, k, Xs, B, X, N, R, r, r_layout, proj, sqnorm);
-  if (D <= 8) return project_fused_dp<KIND, 8>(h, k, Xs, B, X, N, R, r, r_layout, proj, sqnorm);
-  if (D <= 16) return project_fused_dp<KIND, 16>(h, k, Xs, B, X, N, R, r, r_layout, proj, sqnorm);
-  return project_fused_dp<KIND, 32>(h, k, Xs, B, X, N, R, r, r_layout, proj, sqnorm);
-}
-
 template <typename T>
 int project_generic(mgp_handle* h, const mgp_kernel* k, const T* Xs, long B, const T* X, long N, const T* R, int r,
                     int r_layout, T* proj, T* sqnorm) {
@@ -371,20 +353,15 @@ extern "C" int mgp_knm_project(mgp_handle* h, const mgp_kernel* k, const void* X
     return MGP_OK;
   }
   if (!Xs || !X || !R) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
-  if (k->dtype == MGP_F32)
-    return project_generic<float>(h, k, (const float*)Xs, B, (const float*)X, N, (const float*)R, r, r_layout,
-                                  (float*)proj, (float*)sqnorm);
-  if (k->D > MGP_FUSED_MAX_D || r > PJ_MAX_R)
-    return project_generic<double>(h, k, (const double*)Xs, B, (const double*)X, N, (const double*)R, r, r_layout,
-                                   (double*)proj, (double*)sqnorm);
-#define MGP_PJ_K(KV)                                                                                              \
-  return project_fused<KV>(h, k, (const double*)Xs, B, (const double*)X, N, (const double*)R, r, r_layout, \
-                           (double*)proj, (double*)sqnorm)
-  switch (k->kind) {
-    case MGP_SE: MGP_PJ_K(0);
-    case MGP_MATERN12: MGP_PJ_K(1);
-    case MGP_MATERN32: MGP_PJ_K(2);
-    default: MGP_PJ_K(3);
-  }
-#undef MGP_PJ_K
+  if (k->dtype == MGP_F32 || k->D > MGP_FUSED_MAX_D || r > PJ_MAX_R)
+    return mgp_with_dtype(k->dtype, [&](auto t) {
+      using T = decltype(t);
+      return project_generic<T>(h, k, (const T*)Xs, B, (const T*)X, N, (const T*)R, r, r_layout, (T*)proj, (T*)sqnorm);
+    });
+  return mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp(k->D, [&](auto dp) {
+      return project_fused_dp<decltype(kind)::value, decltype(dp)::value>(
+          h, k, (const double*)Xs, B, (const double*)X, N, (const double*)R, r, r_layout, (double*)proj, (double*)sqnorm);
+    });
+  });
 }

@@ -304,25 +304,20 @@ int fused_dispatch_s(mgp_handle* h, const T* X, long N, int D, const T* rec, lon
   }
 }
 
-inline int rff_dp(int D) { return D <= 4 ? 4 : (D <= 8 ? 8 : (D <= 16 ? 16 : 32)); }
-
 template <typename T>
 int sample_fused_t(mgp_handle* h, const T* X, long N, int D, const T* theta, long L, const T* W, int S, T scale,
                    T* out, int layout) {
-  const int DP = rff_dp(D);
-  const long rec_elems = L * (DP + 2L * S);
-  MGP_TRY(mgp_reserve(h, &h->gen, &h->gen_bytes, (size_t)rec_elems * sizeof(T) + 256));
-  T* rec = (T*)h->gen;
-  hipLaunchKernelGGL((rff_pack_records_kernel<T>), dim3((unsigned)((rec_elems + 255) / 256)), dim3(256), 0,
-                     h->stream, theta, L, D, DP, W, S, rec);
-  MGP_LAUNCH_CHECK(h);
-  const long o_sn = layout == MGP_COLS ? S : 1, o_ss = layout == MGP_COLS ? 1 : N;
-  switch (DP) {
-    case 4: return fused_dispatch_s<T, 4>(h, X, N, D, rec, L, S, scale, out, o_sn, o_ss);
-    case 8: return fused_dispatch_s<T, 8>(h, X, N, D, rec, L, S, scale, out, o_sn, o_ss);
-    case 16: return fused_dispatch_s<T, 16>(h, X, N, D, rec, L, S, scale, out, o_sn, o_ss);
-    default: return fused_dispatch_s<T, 32>(h, X, N, D, rec, L, S, scale, out, o_sn, o_ss);
-  }
+  return mgp_with_dp<4>(D, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    const long rec_elems = L * (DP + 2L * S);
+    MGP_TRY(mgp_reserve(h, &h->gen, &h->gen_bytes, (size_t)rec_elems * sizeof(T) + 256));
+    T* rec = (T*)h->gen;
+    hipLaunchKernelGGL((rff_pack_records_kernel<T>), dim3((unsigned)((rec_elems + 255) / 256)), dim3(256), 0,
+                       h->stream, theta, L, D, DP, W, S, rec);
+    MGP_LAUNCH_CHECK(h);
+    const long o_sn = layout == MGP_COLS ? S : 1, o_ss = layout == MGP_COLS ? 1 : N;
+    return fused_dispatch_s<T, DP>(h, X, N, D, rec, L, S, scale, out, o_sn, o_ss);
+  });
 }
 
 // MGP_RFF_ROUTE=panel | fused (A/B runs; read per call so one process can alternate); default: fused where eligible
@@ -349,9 +344,10 @@ extern "C" int mgp_rff_features(mgp_handle* h, int dtype, const void* X, int64_t
   if (ld < 2 * L) return mgp_fail(h, MGP_E_SHAPE, "rff_features: ld=%ld < 2L=%ld", (long)ld, (long)(2 * L));
   if (N == 0 || L == 0) return MGP_OK;
   if (!out) return mgp_fail(h, MGP_E_BADARG, "rff_features: NULL out");
-  if (dtype == MGP_F64)
-    return features_t<double>(h, (const double*)X, N, D, (const double*)theta, L, (double*)out, ld);
-  return features_t<float>(h, (const float*)X, N, D, (const float*)theta, L, (float*)out, ld);
+  return mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    return features_t<T>(h, (const T*)X, N, D, (const T*)theta, L, (T*)out, ld);
+  });
 }
 
 extern "C" int mgp_rff_sample(mgp_handle* h, int dtype, const void* X, int64_t N, int32_t D, const void* theta,
@@ -369,11 +365,9 @@ extern "C" int mgp_rff_sample(mgp_handle* h, int dtype, const void* X, int64_t N
   }
   if (!W) return mgp_fail(h, MGP_E_BADARG, "rff_sample: NULL W");
   const bool fused = rff_use_fused(D, S);
-  if (dtype == MGP_F64) {
-    auto f = fused ? sample_fused_t<double> : sample_panel_t<double>;
-    return f(h, (const double*)X, N, D, (const double*)theta, L, (const double*)W, S, scale, (double*)out, out_layout);
-  }
-  auto f = fused ? sample_fused_t<float> : sample_panel_t<float>;
-  return f(h, (const float*)X, N, D, (const float*)theta, L, (const float*)W, S, (float)scale, (float*)out,
-           out_layout);
+  return mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    auto f = fused ? sample_fused_t<T> : sample_panel_t<T>;
+    return f(h, (const T*)X, N, D, (const T*)theta, L, (const T*)W, S, (T)scale, (T*)out, out_layout);
+  });
 }

@@ -1032,67 +1032,6 @@ int sweep_rc(mgp_handle* h, const SweepParams& prm, int D, const T* A, long na, 
   return MGP_OK;
 }
 
-template <typename T, int KIND>
-int sweep_sq_dp(mgp_handle* h, const SweepParams& prm, int D, const T* A, long na, const T* B, long nb, const T* one,
-                T* out) {
-#define MGP_SQ_CASE(DPV)                                                                                      \
-  return launch_sweep<T, DPV, KIND, 1, true>(h, prm, D, A, na, B, nb, one, 0L, 0L, out, 1L, na, (T)0, nullptr, 0L, \
-                                             0L, nullptr)
-  if (D <= 2) MGP_SQ_CASE(2);
-  if (D <= 4) MGP_SQ_CASE(4);
-  if (D <= 8) MGP_SQ_CASE(8);
-  if (D <= 16) MGP_SQ_CASE(16);
-  MGP_SQ_CASE(32);
-#undef MGP_SQ_CASE
-}
-
-template <typename T>
-int sweep_sq_kind(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const T* B, long nb, const T* one, T* out) {
-  const SweepParams prm = mgp_make_params(k);
-  switch (k->kind) {
-    case MGP_SE: return sweep_sq_dp<T, 0>(h, prm, k->D, A, na, B, nb, one, out);
-    case MGP_MATERN12: return sweep_sq_dp<T, 1>(h, prm, k->D, A, na, B, nb, one, out);
-    case MGP_MATERN32: return sweep_sq_dp<T, 2>(h, prm, k->D, A, na, B, nb, one, out);
-    default: return sweep_sq_dp<T, 3>(h, prm, k->D, A, na, B, nb, one, out);
-  }
-}
-
-template <typename T, int KIND>
-int sweep_dp(mgp_handle* h, const SweepParams& prm, int D, const T* A, long na, const T* B, long nb, const T* W,
-             long w_sj, long w_sr, int R, T* out, long o_si, long o_sr, T alpha, const T* addend, long ad_si,
-             long ad_sr, const int* gate) {
-#define MGP_DP_CASE(DPV)                                                                                   \
-  return sweep_rc<T, DPV, KIND>(h, prm, D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, \
-                                ad_si, ad_sr, gate)
-  if (D <= 2) MGP_DP_CASE(2);
-  if (D <= 4) MGP_DP_CASE(4);
-  if (D <= 8) MGP_DP_CASE(8);
-  if (D <= 16) MGP_DP_CASE(16);
-  MGP_DP_CASE(32);
-#undef MGP_DP_CASE
-}
-
-template <typename T>
-int sweep_kind(mgp_handle* h, const mgp_kernel* k, const T* A, long na, const T* B, long nb, const T* W,
-               long w_sj, long w_sr, int R, T* out, long o_si, long o_sr, T alpha, const T* addend, long ad_si,
-               long ad_sr, const int* gate) {
-  const SweepParams prm = mgp_make_params(k);
-  switch (k->kind) {
-    case MGP_SE:
-      return sweep_dp<T, 0>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si,
-                            ad_sr, gate);
-    case MGP_MATERN12:
-      return sweep_dp<T, 1>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si,
-                            ad_sr, gate);
-    case MGP_MATERN32:
-      return sweep_dp<T, 2>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si,
-                            ad_sr, gate);
-    default:
-      return sweep_dp<T, 3>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si,
-                            ad_sr, gate);
-  }
-}
-
 // out(i, r) = alpha * addend(i, r) (or 0): the product over an empty streamed set
 template <typename T>
 __global__ __launch_bounds__(256) void empty_sum_kernel(T* __restrict__ out, long o_si, long o_sr, long na, int R,
@@ -1118,12 +1057,12 @@ int mgp_sweep(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, con
     // the reference gives for a [B,0].[0,R] contraction (models.py:351 with an empty Kmn)
     const long tot = (long)na * R;
     const unsigned g = (unsigned)((tot + 255) / 256);
-    if (k->dtype == MGP_F64)
-      hipLaunchKernelGGL((empty_sum_kernel<double>), dim3(g), dim3(256), 0, h->stream, (double*)out.base, out.si,
-                         out.sr, (long)na, R, alpha, (const double*)addend.base, addend.si, addend.sr, gate);
-    else
-      hipLaunchKernelGGL((empty_sum_kernel<float>), dim3(g), dim3(256), 0, h->stream, (float*)out.base, out.si, out.sr,
-                         (long)na, R, (float)alpha, (const float*)addend.base, addend.si, addend.sr, gate);
+    mgp_with_dtype(k->dtype, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((empty_sum_kernel<T>), dim3(g), dim3(256), 0, h->stream, (T*)out.base, out.si, out.sr, (long)na,
+                         R, (T)alpha, (const T*)addend.base, addend.si, addend.sr, gate);
+      return MGP_OK;
+    });
     MGP_LAUNCH_CHECK(h);
     return MGP_OK;
   }
@@ -1132,13 +1071,17 @@ int mgp_sweep(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, con
     return mgp_sweep_mfma_f64(h, k, (const double*)A, na, (const double*)B, nb, (const double*)W.base, W.si, W.sr,
                               R, (double*)out.base, out.si, out.sr, alpha, (const double*)addend.base, addend.si,
                               addend.sr, gate);
-  if (k->dtype == MGP_F64)
-    return sweep_kind<double>(h, k, (const double*)A, na, (const double*)B, nb, (const double*)W.base, W.si,
-                              W.sr, R, (double*)out.base, out.si, out.sr, alpha, (const double*)addend.base,
-                              addend.si, addend.sr, gate);
-  return sweep_kind<float>(h, k, (const float*)A, na, (const float*)B, nb, (const float*)W.base, W.si, W.sr, R,
-                           (float*)out.base, out.si, out.sr, (float)alpha, (const float*)addend.base, addend.si,
-                           addend.sr, gate);
+  const SweepParams prm = mgp_make_params(k);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    return mgp_with_kind(k->kind, [&](auto kind) {
+      return mgp_with_dp(k->D, [&](auto dp) {
+        return sweep_rc<T, decltype(dp)::value, decltype(kind)::value>(
+            h, prm, k->D, (const T*)A, na, (const T*)B, nb, (const T*)W.base, W.si, W.sr, R, (T*)out.base, out.si,
+            out.sr, (T)alpha, (const T*)addend.base, addend.si, addend.sr, gate);
+      });
+    });
+  });
 }
 
 // out[m] = sum_i k(x_i, z_m)^2 = diag(K_mn K_nm)
@@ -1153,11 +1096,17 @@ extern "C" int mgp_kmn_sq_colsum(mgp_handle* h, const mgp_kernel* k, const void*
     return MGP_OK;
   }
   if (k->D > MGP_FUSED_MAX_D) return mgp_kmn_sq_colsum_generic(h, k, X, N, Z, M, out);  // generic.hip: explicit panels
-  if (k->dtype == MGP_F64)
-    return sweep_sq_kind<double>(h, k, (const double*)Z, M, (const double*)X, N, (const double*)h->ones,
-                                 (double*)out);
-  return sweep_sq_kind<float>(h, k, (const float*)Z, M, (const float*)X, N, (const float*)((char*)h->ones + 8),
-                              (float*)out);
+  const SweepParams prm = mgp_make_params(k);
+  return mgp_with_dtype(k->dtype, [&](auto t) {
+    using T = decltype(t);
+    const T* one = (const T*)((const char*)h->ones + (sizeof(T) == 8 ? 0 : 8));  // double 1.0 at +0, float 1.0f at +8
+    return mgp_with_kind(k->kind, [&](auto kind) {
+      return mgp_with_dp(k->D, [&](auto dp) {
+        return launch_sweep<T, decltype(dp)::value, decltype(kind)::value, 1, true>(
+            h, prm, k->D, (const T*)Z, M, (const T*)X, N, one, 0L, 0L, (T*)out, 1L, M, (T)0, nullptr, 0L, 0L, nullptr);
+      });
+    });
+  });
 }
 
 extern "C" int mgp_knm_matvec(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z,

@@ -280,18 +280,8 @@ int mgp_sweep_mfma_f64(mgp_handle* h, const mgp_kernel* k, const double* A, long
                        const double* W, long w_sj, long w_sr, int R, double* out, long o_si, long o_sr,
                        double alpha, const double* addend, long ad_si, long ad_sr, const int* gate) {
   const SweepParams prm = mgp_make_params(k);
-  switch (k->kind) {
-    case MGP_SE:
-      return mfma_ks<0>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si, ad_sr,
-                        gate);
-    case MGP_MATERN12:
-      return mfma_ks<1>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si, ad_sr,
-                        gate);
-    case MGP_MATERN32:
-      return mfma_ks<2>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si, ad_sr,
-                        gate);
-    default:
-      return mfma_ks<3>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend, ad_si, ad_sr,
-                        gate);
-  }
+  return mgp_with_kind(k->kind, [&](auto kind) {
+    return mfma_ks<decltype(kind)::value>(h, prm, k->D, A, na, B, nb, W, w_sj, w_sr, R, out, o_si, o_sr, alpha, addend,
+                                          ad_si, ad_sr, gate);
+  });
 }

@@ -171,10 +171,10 @@ FORMS = [
                 "test_symm_matmul_ragged_gemm_regime)", ref="fp64 (as that test)", bar="1e-12"),
     dict(id="kdense_ta16", env={"MGP_KDENSE_TA": "16"}, entry="k_dense",
          cases=[("se", 3, 40, 300), ("matern12", 9, 63, 257), ("matern32", 17, 1, 65), ("matern52", 32, 63, 100)],
-         routes="k_dense_dp: ta 16 at every D", ref="long double", bar="1e-12 (fp64), 3e-5 (fp32)"),
+         routes="k_dense_t: ta 16 at every D", ref="long double", bar="1e-12 (fp64), 3e-5 (fp32)"),
     dict(id="kdense_ta64", env={"MGP_KDENSE_TA": "64"}, entry="k_dense",
          cases=[("se", 3, 40, 300), ("matern12", 8, 63, 257), ("matern32", 17, 1, 65), ("matern52", 9, 63, 100)],
-         routes="k_dense_dp: ta 64 at every D, also N < 64", ref="long double", bar="1e-12 (fp64), 3e-5 (fp32)"),
+         routes="k_dense_t: ta 64 at every D, also N < 64", ref="long double", bar="1e-12 (fp64), 3e-5 (fp32)"),
     # -------- CG on a dense matrix: (n, Bt)
     dict(id="skinny_defer_0", env={"MGP_SKINNY_DEFER": "0"}, entry="cg", cases=[(1500, 9), (1001, 40), (600, 16)],
          routes="cg.hip: Bt above the tile scheme's columns -> skinny product; slices reduced by skinny_reduce_kernel",
