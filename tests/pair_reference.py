@@ -71,7 +71,7 @@ def _sqrt_const(v):
     return hi, ((LD(v) - p) - e) / (LD(2) * hi)
 
 
-def _r2(Xb, Zc, ls):
+def r2(Xb, Zc, ls):
     """r^2 = sum_d ((x_d - z_d) / l_d)^2 as hi + lo (relative error ~2^-120), and w = (x - z) / l.  Xb [n, D], Zc [C, D]."""
     d_hi, d_lo = _two_sum(Xb[:, None, :], -Zc[None, :, :])  # exact: both are fp64 values
     q1 = d_hi / ls
@@ -88,7 +88,7 @@ def _r2(Xb, Zc, ls):
     return hi, lo, q1
 
 
-def _k_over_variance(name, hi, lo):
+def k_over_variance(name, hi, lo):
     """f = k / variance at r^2 = hi + lo."""
     if name == "se":
         return np.exp(LD(-0.5) * hi) * (LD(1) - LD(0.5) * lo)
@@ -142,8 +142,8 @@ def pair_values(name, variance, ls, X, Z, cols=None, derivs=False, block=2048):
     dl = np.empty((n, C, D), dtype=LD) if derivs else None
     dz = np.empty((n, C, D), dtype=LD) if derivs else None
     for i0 in range(0, n, block):
-        hi, lo, w = _r2(X[i0:i0 + block], Zc, ls)
-        f = _k_over_variance(name, hi, lo)
+        hi, lo, w = r2(X[i0:i0 + block], Zc, ls)
+        f = k_over_variance(name, hi, lo)
         k[i0:i0 + block] = var * f
         s[i0:i0 + block] = c2 * hi
         if derivs:
@@ -192,8 +192,14 @@ def pair_bound(name, variance, s, q, a, b, D, dtype):
     fmas and the product with 2^(-q)), 1u the product with the variance; rounded up.
     Below the flush floor (k* < variance 2^-990 in fp64, 2^-120 in fp32) the bound does not apply: see `check_pairs`."""
     del variance
+    return value_bound(name, distance_bound(a, b, D, dtype), q, dtype)
+
+
+def value_bound(name, ds, q, dtype):
+    """The value part of `pair_bound` for a given bound `ds` on |Delta s| (tests/assign_reference.py passes the direct
+    form's bound, or adds what its float64 reference leaves): ln2 ds + F u (SE), ln2 min(ds / q*, sqrt ds) + 2 u ln2 q*
+    + F u (Matern)."""
     u = unit_roundoff(dtype)
-    ds = distance_bound(a, b, D, dtype)
     ln2 = float(np.log(2.0))
     if name == "se":
         return ln2 * ds + FUNCTION_BUDGET * u

@@ -203,6 +203,26 @@ def c3_cdgp():
     torch.cuda.empty_cache()
 
 
+def test_c3_assignment_rows_against_the_float64_reference(c3_cdgp):
+    """The fixture's `u` and `counts` are the device's own; this holds the assignment behind them, at C3's own shape
+    (N = 2^20, D = 8: four rows per thread), to the rule of tests/assign_reference.py on the first 2 rows, the last 1061
+    (the tail block) and 4096 random ones -- rows are independent, so a sample checks the kernel at this shape."""
+    import assign_reference
+    from cggp import ops
+    syn, m, probes, ko, u, counts, Kmm, KL = c3_cdgp
+    N, D = syn.X.shape
+    assert assign_reference.rows_per_thread(N, D, torch.cuda.get_device_properties(0).multi_processor_count) == 4
+    idx, best = ops.nearest_center(m.kernel.spec(D), torch.from_numpy(syn.X).to(dev()), torch.from_numpy(syn.Z).to(dev()))
+    idx, best = idx.cpu().numpy(), best.cpu().numpy()
+    assert idx.min() >= 0 and idx.max() < syn.Z.shape[0]
+    assert np.array_equal(counts[:, 0], np.bincount(idx, minlength=syn.Z.shape[0]))
+    rows = np.unique(np.r_[0, 1, N - 1061:N, np.random.default_rng(8).integers(0, N, 4096)])
+    rep = assign_reference.check_assignment("C3 sqeuclidean", 0, "se", 1.0, np.ones(D), syn.X[rows], syn.Z, idx[rows],
+                                            best[rows])
+    assert np.array_equal(idx[rows][rep.decided], rep.ref_idx[rep.decided])
+    print(f"C3: {rows.size} rows, undecided {rep.undecided_share:.2%}, best err / bound {rep.best_ratio:.3f}")
+
+
 def test_c3_prior_kl_64_probes_m4096(c3_cdgp):
     """`CGGP.prior_kl` with P=64 injected Rademacher probes at M=4096 (`cggp/models.py:293-322`)."""
     from cggp.conjugate_gradient import ConjugateGradient

@@ -51,6 +51,7 @@ def test_factor_against_long_double_with_forced_pivots(kind, D, N):
     assert L.shape == (k, N) and piv.shape == (k,) and diag.shape == (N,)
     piv = piv.cpu().numpy()
     assert len(set(piv.tolist())) == k and piv.min() >= 0 and piv.max() < N  # distinct pivots
+    assert piv[0] == 0  # step 0 is an N-way tie (d = variance everywhere): the lowest index
     rows = kernel_rows(kind, var, ls, X, piv)
     Lr, before, dr = forced_pivoted_cholesky(lambda p: rows[list(piv).index(p)], np.full(N, LD(var)), list(piv))
     Ld = L.cpu().numpy()
@@ -72,6 +73,7 @@ def test_factor_against_long_double_with_forced_pivots(kind, D, N):
     for a in range(DUP):
         b = N - DUP + a
         assert not (a in chosen and b in chosen)
+        assert b not in chosen  # equal rows have equal residuals, bit for bit, until one is taken: the lower index first
         if a in chosen or b in chosen:
             assert dd[a] <= 1e-10 and dd[b] <= 1e-10
 
@@ -94,6 +96,7 @@ def test_rel_tol_stop_matches_the_reference_and_two_calls_are_bit_identical():
     b = ops.kxx_pivchol(spec8, T(X8), 96)
     assert a[0].shape == (96, 70001)
     assert all(torch.equal(x, y) for x, y in zip(a, b))
+    assert int(a[1][0]) == 0  # the N-way tie of step 0 across many workgroups: the lowest index
     # max_rank > N is clamped; N = 0 gives rank 0
     Ls, ps, _ = ops.kxx_pivchol(ops.KernelSpec("matern12", 1.0, [1.0, 1.0], 2), T(np.random.default_rng(0).random((5, 2))), 9)
     assert Ls.shape == (5, 5) and sorted(ps.tolist()) == [0, 1, 2, 3, 4]
