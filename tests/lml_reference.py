@@ -25,9 +25,10 @@ def _profile(name, r2):
     return (LD(1) + s5 * r + LD(5) / LD(3) * r2) * e, np.where(floor, LD(0), LD(-5) / LD(6) * (LD(1) + s5 * r) * e)
 
 
-def kxx_grad_reference(name, variance, lengthscales, X, U, V, block=64):
+def kxx_grad_reference(name, variance, lengthscales, X, U, V, block=64, rows=None):
     """(dvariance, dlengthscales [D]) = sum_r u_r^T dK/dtheta v_r in long double, and the same sums of |terms| (the
-    scale the tests measure rounding against).  U, V [N, R]."""
+    scale the tests measure rounding against).  U, V [N, R].  rows: the rows of U that are not all zero, when the
+    caller knows them -- only their pairs (i, all j) are visited (the others contribute exact zeros)."""
     X = np.asarray(X, dtype=LD)
     U, V = np.asarray(U, dtype=LD), np.asarray(V, dtype=LD)
     ls = np.asarray(lengthscales, dtype=LD).reshape(-1)
@@ -38,12 +39,19 @@ def kxx_grad_reference(name, variance, lengthscales, X, U, V, block=64):
     D = X.shape[1]
     dv, dl = LD(0), np.zeros(D, dtype=LD)
     sv, sl = LD(0), np.zeros(D, dtype=LD)
-    for i0 in range(0, X.shape[0], block):
-        diff = Xs[i0:i0 + block, None, :] - Xs[None, :, :]
+    if rows is None:
+        rows = np.arange(X.shape[0])
+    rows = np.asarray(rows, dtype=np.int64)
+    outside = np.ones(X.shape[0], dtype=bool)
+    outside[rows] = False
+    assert not np.any(U[outside]), "rows must contain every nonzero row of U"
+    for b0 in range(0, rows.shape[0], block):
+        sel = rows[b0:b0 + block]
+        diff = Xs[sel, None, :] - Xs[None, :, :]
         d2 = diff * diff
         r2 = d2.sum(axis=2)
         f, fp = _profile(name, r2)
-        G = U[i0:i0 + block] @ V.T
+        G = U[sel] @ V.T
         dv += np.sum(G * f)
         sv += np.sum(np.abs(G * f))
         w = (G * fp)[:, :, None] * d2 * (var * LD(-2) / ls)

@@ -389,6 +389,38 @@ def test_gpr_cg_against_cholesky(kind):
     assert not auto.uses_cholesky()
 
 
+@pytest.mark.parametrize("kind", ["se", "matern32"])
+def test_gpr_cg_variance_chunks(kind):
+    """`variance_chunk_bytes = 8 N 8` makes predict_f solve its B = 37 test columns in chunks of 8: five, the last of 5
+    (`var[c0:c0 + step]`, `cov[:, c0:c0 + step]`).  The chunked run must equal the single-chunk run.  The device CG
+    iterates a batch until its slowest column is under the threshold (csrc/cg.hip: `while any_b(0.5 |r_b|^2 > thr)`),
+    so a column may take more steps beside 36 others than beside 7 and bit-equality is not promised; the runs are
+    held to 1e-12 absolute instead, the rounding level of these entries (at most the prior variance 1, each a
+    difference of two 300-term sums: about 300 u = 3e-14 apiece), not a bar made from the CG threshold.  Both must
+    meet the Cholesky model at the bar of test_gpr_cg_against_cholesky."""
+    N, D, s2, B, thr = 300, 3, 0.1, 37, 1e-18
+    X, Y, Xs = gpr_data(N, D, seed=5)
+    Xs = Xs[:B]
+    kern = KCLS[kind](1.0, [0.9, 1.2, 0.7])
+    data = (T(X), T(Y))
+    cg = lambda **kw: models.GPR(data, kern, noise_variance=s2, solver="cg",
+                                 conjugate_gradient=ConjugateGradient(thr, max_iterations=1200), **kw)
+    one, chunked = cg(), cg(variance_chunk_bytes=8 * N * 8)
+    assert chunked.variance_chunk_bytes // (N * 8) == 8 and -(-B // 8) == 5 and B % 8 == 5
+    chol = models.GPR(data, kern, noise_variance=s2, solver="cholesky")
+    for full_cov in (False, True):
+        m0, v0 = chol.predict_f(T(Xs), full_cov=full_cov)
+        m1, v1 = one.predict_f(T(Xs), full_cov=full_cov)
+        m2, v2 = chunked.predict_f(T(Xs), full_cov=full_cov)
+        assert v2.shape == v0.shape == ((1, B, B) if full_cov else (B, 1))
+        assert torch.equal(m1, m2)  # the mean does not go through the chunks
+        gap = float((v1 - v2).abs().max())
+        print(f"gpr variance chunks {kind} full_cov={full_cov}: chunked - single {gap:.2e} (bar 1e-12)")
+        assert float(v0.abs().max()) <= 1.0 + 1e-9 and gap <= 1e-12
+        for v in (v1, v2):
+            assert relmax(v, v0.cpu().numpy()) < 1e-6 and relmax(m2, m0.cpu().numpy()) < 1e-6
+
+
 def test_gpr_caches_follow_parameters():
     X, Y, Xs = gpr_data(500, 2, seed=3)
     kern = kernels.SquaredExponential(1.0, [1.0, 1.0])

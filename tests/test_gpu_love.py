@@ -210,6 +210,15 @@ def test_project_workspace_within_stated_bound(route):
             bound += 8 * 8 * c * r  # the NT GEMM's own slices of its [c, r] output (at most 8) in the shared arena
         # a growing handle rounds each arena up by a quarter (+ 4 KiB) and counts 256 bytes of slack per arena
         assert 0 < used <= 1.25 * bound + 2 * (4096 + 256)
+        # the norms themselves, against torch in fp64 (direct differences); on the generic route the call crossed a
+        # test-row and a streamed cut (tests/test_gpu_seams.py checks both sides of each in long double)
+        Xd, Xsd = T(X), T(Xs)
+        r2 = torch.zeros((B, N), dtype=torch.float64, device=dev())
+        for d in range(D):
+            diff = (Xsd[:, d, None] - Xd[None, :, d]) / float(ls[d])
+            r2.addcmul_(diff, diff)
+        ref = torch.exp(-0.5 * r2) @ T(R)
+        assert relmax(sq, (ref * ref).sum(dim=1).cpu().numpy()) < bar("se")
     finally:
         lib.mgp_destroy(h)
 

@@ -38,10 +38,13 @@ def exact_parts(X, th, rows):
     return np.cos(P), np.sin(P), Pabs
 
 
-def spot_rows(N, rng, k=200):
+def spot_rows(N, rng, k=200, panel_rows=None):
+    """The first and last row, k random ones and, for every multiple c of the panel route's row count inside N
+    (`sample_panel_t` starts a new panel there: `out + i0`, `X + i0 * D`), the rows c - 1, c and c + 1."""
     if N <= k:
         return np.arange(N)
-    return np.unique(np.concatenate([[0, N - 1], rng.choice(N, k, replace=False)]))
+    seams = [] if not panel_rows else [i for c in range(panel_rows, N, panel_rows) for i in (c - 1, c, c + 1) if i < N]
+    return np.unique(np.concatenate([[0, N - 1], rng.choice(N, k, replace=False), seams]).astype(np.int64))
 
 
 def check_case(D, S, L, N, dtype, layout, route, monkeypatch, theta_kind="se", lscale=1.0, seed=0):
@@ -72,7 +75,8 @@ def check_case(D, S, L, N, dtype, layout, route, monkeypatch, theta_kind="se", l
     if N == 0:
         return None
     u = U[dtype]
-    rows = spot_rows(N, rng)
+    # rows of Phi per panel: 2^28 / (2 L elem) (csrc/rff.hip, sample_panel_t): 16384 at fp64 and 32768 at fp32 for L = 1024
+    rows = spot_rows(N, rng, panel_rows=(1 << 28) // (2 * L * (4 if dtype == torch.float32 else 8)) if L else None)
     cos, sin, Pabs = exact_parts(X, th, rows)
     # features
     feat_bound = 8 * u * (1 + Pabs)

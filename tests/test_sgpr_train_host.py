@@ -59,6 +59,36 @@ def test_adjoints_composed_with_long_double_vjp_match_autograd(name):
     assert close(kz.numpy() + nz.astype(np.float64), gZ.numpy())
 
 
+@pytest.mark.parametrize("name", KERNELS)
+def test_kmm_grad_z_row_chunks(name):
+    """`max_elems = 7 M D` makes kmm_grad_z walk its M = 30 rows in chunks of 7: five, the last of 2.  Against the
+    default (one chunk) at 1e-14 relative, and against autograd through a direct-difference kernel matrix written here,
+    L = sum(G * k(Z, Z)), at 1e-12 relative."""
+    M, D = 30, 3
+    rng = np.random.default_rng(11)
+    Z = torch.tensor(rng.uniform(-1.5, 1.5, (M, D)))
+    G = torch.tensor(rng.standard_normal((M, M)))
+    var, ls = 1.3, [0.9, 1.2, 0.7]
+    chunked = training.kmm_grad_z(name, var, ls, Z, G, max_elems=7 * M * D)
+    assert 7 * M * D // (M * D) == 7 and -(-M // 7) == 5 and M % 7 == 2
+    whole = training.kmm_grad_z(name, var, ls, Z, G)
+    scale = float(whole.abs().max())
+    assert float((chunked - whole).abs().max()) <= 1e-14 * scale
+
+    Zt = Z.clone().requires_grad_()
+    diff = (Zt[:, None, :] - Zt[None, :, :]) / torch.tensor(ls, dtype=torch.float64)
+    r2 = (diff * diff).sum(dim=2)
+    if name == "se":
+        K = var * torch.exp(-0.5 * r2)
+    else:
+        r = torch.sqrt(torch.clamp(r2, min=1e-36))  # GPflow's floor: no gradient through the diagonal's r = 0
+        c = {"matern12": 1.0, "matern32": 3.0 ** 0.5, "matern52": 5.0 ** 0.5}[name]
+        poly = {"matern12": 1.0, "matern32": 1.0 + c * r, "matern52": 1.0 + c * r + 5.0 / 3.0 * r * r}[name]
+        K = var * poly * torch.exp(-c * r)
+    (gz,) = torch.autograd.grad((G * K).sum(), [Zt])
+    assert float((chunked - gz).abs().max()) <= 1e-12 * float(gz.abs().max())
+
+
 def test_kmm_grad_z_is_zero_on_duplicate_inducing_points_for_matern12():
     Z = torch.tensor([[0.1, 0.2], [0.1, 0.2], [1.0, -0.5]], dtype=torch.float64)
     G = torch.ones(3, 3, dtype=torch.float64)
