@@ -14,6 +14,11 @@
 // no-ops -- the step count stays exactly the reference's.  The host polls `active` once per
 // batch.  Vectors are [Bt, n] row-major (the function-level layout, :24-32); one workgroup owns
 // one right-hand side, dot products are wavefront shuffles + one LDS hop.
+//
+// Host side: apply_operator (A.p for every operator kind) and pcg_solve_t, which reads decode_precond -> routes ->
+// CgArena -> CgSolve::start -> one of run_persist / run_dense1_pipelined / run_polled -> statistics (read_ctrl: the one
+// poll of the control word; enqueue_batch: the one batch body).  An operator form that leaves A.p somewhere other than
+// `out` says so through the MgpApLoc* it was handed (mgp_common.h), never through the handle.
 #include <chrono>
 #include <cstdio>
 
@@ -99,13 +104,15 @@ __global__ __launch_bounds__(256) void cg_init_kernel(const T* __restrict__ b, c
   }
 }
 
-// Generic step pieces (refresh steps, block / dense preconditioners).  Modes:
-//   0  first half (gamma, v, r -= gamma Ap) + native preconditioner + second half
-//   1  first half without the r update (a residual refresh follows)
-//   2  native preconditioner + second half with beta = 0 (after a refresh: p = z)
-//   3  first half only, with the r update (a dense preconditioner product follows)
-//   4  second half with z already in memory (dense preconditioner), normal beta
-//   5  second half with z already in memory, beta = 0 (start-up and refresh: p = z)
+// Generic step pieces (refresh steps, block / dense preconditioners).  The kernel's `mode`:
+enum UpdateMode : int {
+  UPD_STEP = 0,            // first half (gamma, v, r -= gamma Ap) + native preconditioner + second half
+  UPD_STEP_KEEP_R = 1,     // first half without the r update (a residual refresh follows)
+  UPD_RESTART = 2,         // native preconditioner + second half with beta = 0 (after a refresh: p = z)
+  UPD_FIRST_HALF = 3,      // first half only, with the r update (z from outside the kernel follows)
+  UPD_SECOND_HALF = 4,     // second half with z already in memory, normal beta
+  UPD_SECOND_RESTART = 5,  // second half with z already in memory, beta = 0 (start-up and refresh: p = z)
+};
 // `force` bypasses the gate (start-up of the dense-preconditioner path).
 // Block size: 256 threads per right-hand side up to n = 8192, 1024 beyond (the fused kernel covers n <= 8192; one
 // 256-thread workgroup per right-hand side was a cliff for larger systems).
@@ -350,14 +357,6 @@ __global__ void cg_advance_kernel(CgCtrl* ctrl, const int* __restrict__ over, lo
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void axpby_kernel(const int* __restrict__ gate, T a, const T* __restrict__ x, T b,
-                                                    const T* __restrict__ y, T* __restrict__ out, long total) {
-  if (gate != nullptr && *gate == 0) return;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < total) out[i] = a * x[i] + b * y[i];
-}
-
 // t[b, j] += a * x[b, j] for the columns j in [rb, re)
 template <typename T>
 __global__ __launch_bounds__(256) void add_rows_slab_kernel(const int* __restrict__ gate, T a, const T* __restrict__ x,
@@ -404,14 +403,16 @@ __global__ __launch_bounds__(256) void finish_allreduce_kernel(int* __restrict__
 
 inline unsigned nblk(long total) { return (unsigned)((total + 255) / 256); }
 
-
-// out[Bt, n] = P[Bt, n] @ Op ; gate may be null
+// out[Bt, n] = P[Bt, n] @ Op ; gate may be null.  loc (MgpApLoc, mgp_common.h): null = finished into out; else the
+// skinny product may leave its slices and the collective SGPR operator, under a gate, its all-reduced partial
 template <typename T>
-int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T* out, const int* gate) {
+int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T* out, const int* gate,
+                   MgpApLoc* loc = nullptr) {
   const long n = op->n;
+  if (loc != nullptr) *loc = MgpApLoc{out, 1, 0, nullptr, 0};
   switch (op->kind) {
     case MGP_OP_DENSE:
-      return mgp_symm_matmul_gated(h, op->dtype, op->A, n, P, Bt, out, gate);
+      return mgp_symm_matmul_gated(h, op->dtype, op->A, n, P, Bt, out, gate, loc);
     case MGP_OP_KMM_LAMBDA: {
       MGP_TRY(mgp_sweep(h, op->kernel, op->Z, op->M, op->Z, op->M, VecView{P, 1, n}, (int)Bt,
                         VecViewMut{out, 1, n}, 0.0, VecView{nullptr, 0, 0}, gate));
@@ -505,9 +506,8 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
           MGP_TRY(mgp_comm_allreduce_on(h, op->comm, tt, (size_t)(tot + 1), op->dtype));
         }
         const int world = op->comm ? mgp_comm_size(op->comm) : op->world_size;
-        if (h->defer_finish && gate != nullptr) {  // the fused update tests the word and reads the partial in place
-          h->deferred_tt = tt;
-          h->deferred_world = world;
+        if (loc != nullptr && gate != nullptr) {  // the fused update tests the word and reads the partial in place
+          *loc = MgpApLoc{tt, 1, 0, tt + tot, world};
           return MGP_OK;
         }
         hipLaunchKernelGGL((finish_allreduce_kernel<T>), dim3(nblk(tot)), dim3(256), 0, h->stream, (int*)gate,
@@ -552,160 +552,248 @@ int check_operator(mgp_handle* h, const mgp_operator* op) {
 
 constexpr int kRetryWithoutPersist = 1;  // internal: never crosses the C ABI
 
-template <typename T>
-int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const T* B, const T* V0, long Bt,
-                double thr, long max_it, long cycle, double min_float, int check_every, T* V, T* err_out,
-                mgp_cg_stats* stats, T* coef, long coef_steps) {
-  const long n = op->n;
-  const long tot = Bt * n;
-  const auto t0 = std::chrono::steady_clock::now();
-  PackHold pack_hold(h);  // the operator's X / Z / kernel are constant for the whole solve
-  PrecondDev pc{MGP_PRE_EYE, 0, 0, nullptr, nullptr, nullptr};
-  const void* dense_inv = nullptr;  // MGP_PRE_DENSE: z = r @ Pinv through the symmetric product kernels
-  const mgp_precond* cb = nullptr;  // MGP_PRE_CALLBACK: z produced by the caller's function, same step structure
+// ------------------------------------------------------------------ the pieces of pcg_solve_t
+// The caller's mgp_precond: the form the update kernels apply themselves (`dev`; the identity when z comes from outside
+// them) or one of the three external forms
+struct CgPrecond {
+  PrecondDev dev{MGP_PRE_EYE, 0, 0, nullptr, nullptr, nullptr};
+  const void* dense_inv = nullptr;       // MGP_PRE_DENSE: z = r @ Pinv through the symmetric product kernels
+  const mgp_precond* cb = nullptr;       // MGP_PRE_CALLBACK: z produced by the caller's function, same step structure
   const mgp_precond* lowrank = nullptr;  // MGP_PRE_LOWRANK: z = diag_inv o r - (r B^T) B (pivchol.hip)
+  bool dense_pre = false, need_z = false;  // z comes from outside the update kernels; z lives in the arena
+};
+
+int decode_precond(mgp_handle* h, const mgp_precond* pre, CgPrecond& c) {
   if (pre) {
-    pc.kind = pre->kind;
+    c.dev.kind = pre->kind;
     if (pre->kind == MGP_PRE_JACOBI) {
       if (!pre->diag_inv) return mgp_fail(h, MGP_E_BADARG, "jacobi preconditioner without diag_inv");
-      pc.diag_inv = pre->diag_inv;
+      c.dev.diag_inv = pre->diag_inv;
     } else if (pre->kind == MGP_PRE_BLOCK) {
       if (!pre->block_index || !pre->block_inv || pre->block_size <= 0 || pre->num_blocks < 0)
         return mgp_fail(h, MGP_E_BADARG, "block preconditioner incomplete");
-      pc.bs = pre->block_size;
-      pc.nb = pre->num_blocks;
-      pc.block_index = (const long*)pre->block_index;
-      pc.block_inv = pre->block_inv;
+      c.dev.bs = pre->block_size;
+      c.dev.nb = pre->num_blocks;
+      c.dev.block_index = (const long*)pre->block_index;
+      c.dev.block_inv = pre->block_inv;
     } else if (pre->kind == MGP_PRE_DENSE) {
       if (!pre->dense_inv) return mgp_fail(h, MGP_E_BADARG, "dense preconditioner without matrix");
-      dense_inv = pre->dense_inv;
+      c.dense_inv = pre->dense_inv;
     } else if (pre->kind == MGP_PRE_CALLBACK) {
       if (!pre->apply || !pre->cb_r || !pre->cb_z)
         return mgp_fail(h, MGP_E_BADARG, "callback preconditioner needs apply, cb_r and cb_z");
-      cb = pre;
+      c.cb = pre;
     } else if (pre->kind == MGP_PRE_LOWRANK) {
       if (!pre->diag_inv || !pre->dense_inv || pre->num_blocks < 1)
         return mgp_fail(h, MGP_E_BADARG, "low-rank preconditioner needs diag_inv, B (dense_inv) and k (num_blocks) >= 1");
-      lowrank = pre;
+      c.lowrank = pre;
     } else if (pre->kind != MGP_PRE_EYE) {
       return mgp_fail(h, MGP_E_BADARG, "unknown preconditioner kind %d", pre->kind);
     }
   }
-  const bool dense_pre = dense_inv != nullptr || cb != nullptr || lowrank != nullptr;  // z comes from outside the update kernels
-  const bool need_z = pc.kind != MGP_PRE_EYE && cb == nullptr;   // dense: z = r @ Pinv lives in the arena
-  if (dense_pre) pc.kind = MGP_PRE_EYE;                          // the update kernels never apply it themselves
-  // arena: r, p, ap, [z], rz[Bt], over[Bt] (int), ctrl
-  // one right-hand side on a dense matrix, no residual refresh inside the solve: the two-launch iteration of
-  // cg_dense1.hip (tile shares, chunk shares, two direction buffers live behind the control word)
-  // ... and, since round 4, two to eight right-hand sides on the same tile scheme (the reference's default num_probes = 5)
-  // ... up to 8 where the full matrix fits the chip (n <= 2048: the register-resident form carries the columns for 16
-  // fused multiply-adds each), else where the tile scheme was measured faster than the skinny product: 4, 6 above 4096
-  const long d1_cols = h->cg_dense1_cols > 0 ? h->cg_dense1_cols
-                       : ((!h->d1_persist_off && mgp_dense1_persist_eligible(h, n, 8))   ? 8
-                          : (!h->d1_persist_off && mgp_dense1_persist_eligible(h, n, 6)) ? 6
-                                                                                         : (n <= 4096 ? 4 : 6));
-  const bool dense1 = op->kind == MGP_OP_DENSE && Bt >= 1 && Bt <= d1_cols && !dense_pre &&
-                      pc.kind != MGP_PRE_BLOCK && cycle > max_it && mgp_dense1_eligible(h, n) && coef == nullptr;
-  size_t bytes = (size_t)tot * sizeof(T) * (need_z ? 4 : 3) + (size_t)Bt * sizeof(T) + (size_t)Bt * sizeof(int) + 64 +
-                 (dense1 ? mgp_dense1_bytes(h, op->dtype, n, Bt) : 0);
-  MGP_TRY(mgp_reserve(h, &h->cg, &h->cg_bytes, bytes));
-  T* r = (T*)h->cg;
-  T* p = r + tot;
-  T* ap = p + tot;
-  T* z = need_z ? ap + tot : (cb ? (T*)cb->cb_z : nullptr);
-  T* rz = (need_z ? ap + tot : ap) + tot;
-  int* over = (int*)(rz + Bt);
-  CgCtrl* ctrl = (CgCtrl*)(((uintptr_t)(over + Bt) + 15) & ~(uintptr_t)15);
-  void* d1_arena = (void*)(((uintptr_t)(ctrl + 1) + 15) & ~(uintptr_t)15);
-  hipStream_t s = h->stream;
-  const unsigned upd_threads = n > 8192 ? 1024u : 256u;  // generic update kernel: threads per right-hand side
-#define MGP_UPDATE_LAUNCH(...)                                                                                   \
-  do {                                                                                                           \
-    if (upd_threads == 1024u)                                                                                    \
-      hipLaunchKernelGGL((cg_update_kernel<T, 1024>), dim3((unsigned)Bt), dim3(1024), 0, s, __VA_ARGS__);        \
-    else                                                                                                         \
-      hipLaunchKernelGGL((cg_update_kernel<T, 256>), dim3((unsigned)Bt), dim3(256), 0, s, __VA_ARGS__);          \
-  } while (0)
+  c.dense_pre = c.dense_inv != nullptr || c.cb != nullptr || c.lowrank != nullptr;
+  c.need_z = c.dev.kind != MGP_PRE_EYE && c.cb == nullptr;  // dense: z = r @ Pinv lives in the arena
+  if (c.dense_pre) c.dev.kind = MGP_PRE_EYE;                // the update kernels never apply it themselves
+  return MGP_OK;
+}
+
+// The CG arena (h->cg): r, p, ap, [z], rz[Bt], over[Bt] (int), ctrl, then the arena of cg_dense1.hip (tile shares,
+// chunk shares, two direction buffers).  The byte count and the pointers are written here and nowhere else.
+template <typename T>
+struct CgArena {
+  T *r, *p, *ap, *z, *rz;
+  int* over;
+  CgCtrl* ctrl;
+  void* d1_arena;  // 16-byte aligned, as is ctrl
+  // 64: the control word and the two round-ups to 16 bytes below
+  static size_t bytes(long tot, long Bt, bool need_z, size_t d1_bytes) {
+    return (size_t)tot * sizeof(T) * (need_z ? 4 : 3) + (size_t)Bt * sizeof(T) + (size_t)Bt * sizeof(int) + 64 + d1_bytes;
+  }
+  CgArena(void* base, long tot, long Bt, bool need_z) {
+    r = (T*)base;
+    p = r + tot;
+    ap = p + tot;
+    z = need_z ? ap + tot : nullptr;
+    rz = (need_z ? z : ap) + tot;
+    over = (int*)(rz + Bt);
+    ctrl = (CgCtrl*)(((uintptr_t)(over + Bt) + 15) & ~(uintptr_t)15);
+    d1_arena = (void*)(((uintptr_t)(ctrl + 1) + 15) & ~(uintptr_t)15);
+  }
+};
+
+// the device control word on the host: every earlier launch of the stream has finished when this returns
+int read_ctrl(mgp_handle* h, const CgCtrl* ctrl, CgCtrl* host) {
+  MGP_HIP(h, hipMemcpyAsync(h->host_flag, ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, h->stream));
+  MGP_HIP(h, hipStreamSynchronize(h->stream));
+  memcpy(host, h->host_flag, sizeof(CgCtrl));
+  return MGP_OK;
+}
+
+// Fused update kernel: (elements per thread, threads) by system size, one workgroup per right-hand side with its
+// elements in registers
+template <typename T>
+struct FusedTier {
+  long max_n;
+  unsigned nt;
+  decltype(&cg_update_fused_kernel<T, 1, 256>) kernel;
+};
+template <typename T>
+constexpr FusedTier<T> kFusedTiers[] = {
+    {256, 256, cg_update_fused_kernel<T, 1, 256>},    {512, 256, cg_update_fused_kernel<T, 2, 256>},
+    {1024, 1024, cg_update_fused_kernel<T, 1, 1024>}, {2048, 1024, cg_update_fused_kernel<T, 2, 1024>},
+    {4096, 1024, cg_update_fused_kernel<T, 4, 1024>}, {8192, 1024, cg_update_fused_kernel<T, 8, 1024>}};
+constexpr long kFusedMaxN = 8192;
+
+// One solve: its arguments, its routes and its arena, and the launches of a step.
+template <typename T>
+struct CgSolve {
+  mgp_handle* h;
+  const mgp_operator* op;
+  const T* B;
+  long Bt, n, tot, max_it, cycle, check_every, coef_steps;
+  double thr, min_float;
+  T *V, *err_out, *coef;
+  hipStream_t s;
+  CgPrecond pre;
+  CgArena<T> a;
+  T* z;                // the arena's, or the callback's own buffer
+  bool dense1, fused;  // the tile scheme of cg_dense1.hip; cg_update_fused_kernel serves the steps without a refresh
+  MgpDense1 d1;
+  long enq = 0;  // iterations enqueued so far (index of the next one)
+  CgCtrl host{1, 0};
+
   // z = M^-1 r for the preconditioners applied outside the update kernels
-  auto external_z = [&](const int* gate) -> int {
-    if (cb) {
-      MGP_HIP(h, hipMemcpyAsync(cb->cb_r, r, (size_t)tot * sizeof(T), hipMemcpyDeviceToDevice, s));
-      const int rc = cb->apply(cb->apply_ctx, cb->cb_r, cb->cb_z, Bt, n, (void*)s);
+  int external_z(const int* gate) {
+    if (pre.cb) {
+      MGP_HIP(h, hipMemcpyAsync(pre.cb->cb_r, a.r, (size_t)tot * sizeof(T), hipMemcpyDeviceToDevice, s));
+      const int rc = pre.cb->apply(pre.cb->apply_ctx, pre.cb->cb_r, pre.cb->cb_z, Bt, n, (void*)s);
       if (rc != 0) return mgp_fail(h, MGP_E_BADARG, "preconditioner callback returned %d", rc);
       return MGP_OK;
     }
-    if (lowrank)
-      return mgp_lowrank_apply_gated(h, op->dtype, lowrank->diag_inv, lowrank->dense_inv, lowrank->num_blocks, n, r, Bt,
-                                     z, gate);
-    return mgp_symm_matmul_gated(h, op->dtype, dense_inv, n, r, Bt, z, gate);
-  };
-
-  MGP_HIP(h, hipMemsetAsync(ctrl, 0, sizeof(CgCtrl), s));
-  const T* av = nullptr;
-  if (V0) {
-    if (V != V0) MGP_HIP(h, hipMemcpyAsync(V, V0, (size_t)tot * sizeof(T), hipMemcpyDeviceToDevice, s));
-    MGP_TRY(apply_operator<T>(h, op, V, Bt, ap, nullptr));  // vA (:87)
-    av = ap;
-  } else {
-    MGP_HIP(h, hipMemsetAsync(V, 0, (size_t)tot * sizeof(T), s));
+    if (pre.lowrank)
+      return mgp_lowrank_apply_gated(h, op->dtype, pre.lowrank->diag_inv, pre.lowrank->dense_inv,
+                                     pre.lowrank->num_blocks, n, a.r, Bt, z, gate);
+    return mgp_symm_matmul_gated(h, op->dtype, pre.dense_inv, n, a.r, Bt, z, gate);
   }
-  MgpDense1 d1;
-  // n <= 4096: the whole solve in one launch, the upper triangle of A in registers (cg_dense1.hip)
-  const bool persist = dense1 && !h->d1_persist_off && mgp_dense1_persist_eligible(h, n, Bt);
-  if (dense1) {
-    MGP_TRY(mgp_dense1_begin(h, &d1, op->dtype, op->A, n, B, av, V, r,
-                             pc.kind == MGP_PRE_JACOBI ? pc.diag_inv : nullptr, ctrl, d1_arena, thr, min_float, max_it,
-                             persist ? 1 : 0, (int)Bt));
-    MGP_TRY(mgp_dense1_finish(h, &d1, rz, err_out, over));  // statistics of r_0 and the first gate
-    if (persist) {
-      MGP_TRY(mgp_dense1_persist_run(h, &d1));
-      MGP_TRY(mgp_dense1_finish(h, &d1, rz, err_out, over));  // final statistics; closes the gate
+
+  // generic update kernel: 256 threads per right-hand side up to n = 8192, 1024 beyond
+  int update(UpdateMode mode, bool force = false) {
+    const bool records = mode == UPD_STEP || mode == UPD_FIRST_HALF || mode == UPD_SECOND_HALF;  // the recording solve
+    hipLaunchKernelGGL((n > 8192 ? cg_update_kernel<T, 1024> : cg_update_kernel<T, 256>), dim3((unsigned)Bt),
+                       dim3(n > 8192 ? 1024 : 256), 0, s, a.ctrl, V, a.r, a.p, z, a.ap, a.rz, a.over, err_out, n, (T)thr,
+                       (T)min_float, pre.dev, (int)mode, force ? 1 : 0, records ? coef : (T*)nullptr,
+                       records ? coef_steps : 0L);
+    MGP_LAUNCH_CHECK(h);
+    return MGP_OK;
+  }
+
+  int advance(int inc) {
+    hipLaunchKernelGGL(cg_advance_kernel, dim3(1), dim3(256), 0, s, a.ctrl, a.over, Bt, inc, (int)max_it);
+    MGP_LAUNCH_CHECK(h);
+    return MGP_OK;
+  }
+
+  // whole step in one launch, bookkeeping included; A.p is read from wherever the operator left it
+  int fused_update(const MgpApLoc& ap) {
+    const T* dinv = pre.dev.kind == MGP_PRE_JACOBI ? (const T*)pre.dev.diag_inv : nullptr;
+    const FusedTier<T>* t = kFusedTiers<T>;
+    while (n > t->max_n) ++t;  // ends: n <= kFusedMaxN
+    hipLaunchKernelGGL(t->kernel, dim3((unsigned)Bt), dim3(t->nt), 0, s, a.ctrl, V, a.r, a.p, (const T*)ap.src, a.rz, a.over,
+                       err_out, n, (T)thr, (T)min_float, dinv, (int)max_it, ap.slices, ap.stride, (const T*)ap.agree,
+                       ap.world, coef, coef_steps);
+    MGP_LAUNCH_CHECK(h);
+    return MGP_OK;
+  }
+
+  // iteration i of the polled loop, every launch gated by the device word
+  int step(long i) {
+    const int* gate = &a.ctrl->active;
+    const bool reset = (i % cycle) == (cycle - 1);  // :71 (i == state.i while active)
+    const bool fuse = fused && !reset;
+    // only the fused update can read A.p from somewhere else: the skinny product's slices (dense operator) or the
+    // all-reduced partial of the collective SGPR operator, each where its durable switch allows
+    const bool may_defer = fuse && ((op->kind == MGP_OP_DENSE && h->skinny_defer) || (op->kind == MGP_OP_SGPR && h->fuse_agree));
+    MgpApLoc ap{a.ap, 1, 0, nullptr, 0};
+    MGP_TRY(apply_operator<T>(h, op, a.p, Bt, a.ap, gate, may_defer ? &ap : nullptr));
+    if (fuse) return fused_update(ap);
+    if (!reset) {
+      if (!pre.dense_pre) {
+        MGP_TRY(update(UPD_STEP));
+      } else {
+        MGP_TRY(update(UPD_FIRST_HALF));
+        MGP_TRY(external_z(gate));
+        MGP_TRY(update(UPD_SECOND_HALF));
+      }
+    } else {  // r = b - vA (:72-75), p = z
+      MGP_TRY(update(UPD_STEP_KEEP_R));
+      MGP_TRY(apply_operator<T>(h, op, V, Bt, a.ap, gate));
+      hipLaunchKernelGGL((cg_residual_kernel<T>), dim3(nblk(tot)), dim3(256), 0, s, a.ctrl, B, a.ap, a.r, tot, 0);
+      MGP_LAUNCH_CHECK(h);
+      if (pre.dense_pre) MGP_TRY(external_z(gate));
+      MGP_TRY(update(pre.dense_pre ? UPD_SECOND_RESTART : UPD_RESTART));
     }
-  } else if (!dense_pre) {
-    hipLaunchKernelGGL((cg_init_kernel<T>), dim3((unsigned)Bt), dim3(256), 0, s, B, av, r, z, p, rz, over, err_out,
-                       n, (T)thr, pc);
-    MGP_LAUNCH_CHECK(h);
-  } else {  // r = b - vA ; z = r @ Pinv ; p = z, rz = z.r, flags
-    hipLaunchKernelGGL((cg_residual_kernel<T>), dim3(nblk(tot)), dim3(256), 0, s, ctrl, B, av, r, tot, 1);
-    MGP_LAUNCH_CHECK(h);
-    MGP_TRY(external_z(nullptr));
-    MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz, over,
-                       err_out, n, (T)thr, (T)min_float, pc, 5, 1, (T*)nullptr, 0L);
-    MGP_LAUNCH_CHECK(h);
-  }
-  if (!dense1) {
-    hipLaunchKernelGGL(cg_advance_kernel, dim3(1), dim3(256), 0, s, ctrl, over, Bt, 0, (int)max_it);
-    MGP_LAUNCH_CHECK(h);
+    return advance(1);
   }
 
-  // fused step kernel: elements of one RHS in registers.  Code = EPT for 256 threads (n <= 1024),
-  // 14/12/24/8 for 1024 threads with EPT 1/2/4/8 (n <= 8192); 0 = generic loop kernels.
-  int fused_ept = 0;
-  if (pc.kind != MGP_PRE_BLOCK && !dense_pre && Bt < 2147483647L) {
-    if (n <= 256) fused_ept = 1;
-    else if (n <= 512) fused_ept = 2;
-    else if (n <= 1024) fused_ept = 14;
-    else if (n <= 2048) fused_ept = 12;
-    else if (n <= 4096) fused_ept = 24;
-    else if (n <= 8192) fused_ept = 8;
+  // up to check_every iterations back to back; on the tile scheme its statistics launch closes the batch
+  int enqueue_batch() {
+    long batch = check_every;
+    if (enq + batch > max_it) batch = max_it - enq;
+    if (dense1) {
+      for (long q = 0; q < batch; ++q, ++enq) MGP_TRY(mgp_dense1_step(h, &d1, enq + 1));
+      return mgp_dense1_finish(h, &d1, a.rz, err_out, a.over);
+    }
+    for (long q = 0; q < batch; ++q, ++enq) MGP_TRY(step(enq));
+    return MGP_OK;
   }
-  if (check_every < 1) check_every = 1;
-  long enq = 0;  // iterations enqueued so far (index of the next one)
-  CgCtrl host{1, 0};
-  if (persist) {
-    MGP_HIP(h, hipMemcpyAsync(h->host_flag, ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, s));
-    MGP_HIP(h, hipStreamSynchronize(s));
-    memcpy(&host, h->host_flag, sizeof(CgCtrl));
-    // a hand-off ran out of its poll budget (a workgroup was not resident: the chip was shared): the caller retries
-    // this solve with the two-launch form
-    if (host.pad) return kRetryWithoutPersist;
-  } else if (dense1 && h->poll_pipeline) {
-    // One polled batch stays in flight: the device works on batch i + 1 while the host waits for the control word of
-    // batch i (round 3: every poll drained the stream, ~20 us each, 10 of them in a 248-step solve).  When a batch
-    // reports the end, the one behind it is already enqueued -- its launches are gated off on the device.
-    MGP_HIP(h, hipMemcpyAsync(h->host_flag, ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, s));
-    MGP_HIP(h, hipStreamSynchronize(s));
-    memcpy(&host, h->host_flag, sizeof(CgCtrl));
+
+  // r_0, z_0, p_1, the flags and the first gate.  `persist`: the register-resident solve runs here, whole.
+  int start(const T* V0, bool persist) {
+    MGP_HIP(h, hipMemsetAsync(a.ctrl, 0, sizeof(CgCtrl), s));
+    const T* av = nullptr;
+    if (V0) {
+      if (V != V0) MGP_HIP(h, hipMemcpyAsync(V, V0, (size_t)tot * sizeof(T), hipMemcpyDeviceToDevice, s));
+      MGP_TRY(apply_operator<T>(h, op, V, Bt, a.ap, nullptr));  // vA (:87)
+      av = a.ap;
+    } else {
+      MGP_HIP(h, hipMemsetAsync(V, 0, (size_t)tot * sizeof(T), s));
+    }
+    if (dense1) {
+      MGP_TRY(mgp_dense1_begin(h, &d1, op->dtype, op->A, n, B, av, V, a.r,
+                               pre.dev.kind == MGP_PRE_JACOBI ? pre.dev.diag_inv : nullptr, a.ctrl, a.d1_arena, thr,
+                               min_float, max_it, persist ? 1 : 0, (int)Bt));
+      MGP_TRY(mgp_dense1_finish(h, &d1, a.rz, err_out, a.over));  // statistics of r_0 and the first gate
+      if (persist) {
+        MGP_TRY(mgp_dense1_persist_run(h, &d1));
+        MGP_TRY(mgp_dense1_finish(h, &d1, a.rz, err_out, a.over));  // final statistics; closes the gate
+      }
+      return MGP_OK;
+    }
+    if (!pre.dense_pre) {
+      hipLaunchKernelGGL((cg_init_kernel<T>), dim3((unsigned)Bt), dim3(256), 0, s, B, av, a.r, z, a.p, a.rz, a.over,
+                         err_out, n, (T)thr, pre.dev);
+      MGP_LAUNCH_CHECK(h);
+    } else {  // r = b - vA ; z = r @ Pinv ; p = z, rz = z.r, flags
+      hipLaunchKernelGGL((cg_residual_kernel<T>), dim3(nblk(tot)), dim3(256), 0, s, a.ctrl, B, av, a.r, tot, 1);
+      MGP_LAUNCH_CHECK(h);
+      MGP_TRY(external_z(nullptr));
+      MGP_TRY(update(UPD_SECOND_RESTART, true));
+    }
+    return advance(0);
+  }
+
+  // n <= 4096: the whole solve ran in one launch (start); what is left is its verdict.  A hand-off ran out of its poll
+  // budget (a workgroup was not resident: the chip was shared): the caller retries this solve with the two-launch form
+  int run_persist() {
+    MGP_TRY(read_ctrl(h, a.ctrl, &host));
+    return host.pad ? kRetryWithoutPersist : MGP_OK;
+  }
+
+  // Tile scheme, one polled batch stays in flight: the device works on batch i + 1 while the host waits for the
+  // control word of batch i (every poll drained the stream, ~20 us each, 10 of them in a 248-step solve).  When a
+  // batch reports the end, the one behind it is already enqueued -- its launches are gated off on the device.
+  int run_dense1_pipelined() {
+    MGP_TRY(read_ctrl(h, a.ctrl, &host));
     for (int e = 0; e < 2; ++e)
       if (!h->poll_ev[e]) MGP_HIP(h, hipEventCreateWithFlags(&h->poll_ev[e], hipEventDisableTiming));
     CgCtrl* slots = (CgCtrl*)h->host_flag;  // 64 pinned bytes: two control words fit behind the first
@@ -713,11 +801,8 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
     bool more = host.active != 0;
     while (more || inflight > 0) {
       while (more && inflight < 2 && enq < max_it) {
-        long batch = check_every;
-        if (enq + batch > max_it) batch = max_it - enq;
-        for (long q = 0; q < batch; ++q, ++enq) MGP_TRY(mgp_dense1_step(h, &d1, enq + 1));
-        MGP_TRY(mgp_dense1_finish(h, &d1, rz, err_out, over));
-        MGP_HIP(h, hipMemcpyAsync(&slots[1 + wr], ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, s));
+        MGP_TRY(enqueue_batch());
+        MGP_HIP(h, hipMemcpyAsync(&slots[1 + wr], a.ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, s));
         MGP_HIP(h, hipEventRecord(h->poll_ev[wr], s));
         wr ^= 1;
         ++inflight;
@@ -731,120 +816,68 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
       if (!host.active || enq >= max_it) more = false;
       if (!host.active) break;  // what is still in flight does nothing (device gate); no need to wait for it
     }
+    return MGP_OK;
   }
-  while (!persist && !(dense1 && h->poll_pipeline)) {
-    MGP_HIP(h, hipMemcpyAsync(h->host_flag, ctrl, sizeof(CgCtrl), hipMemcpyDeviceToHost, s));
-    MGP_HIP(h, hipStreamSynchronize(s));
-    memcpy(&host, h->host_flag, sizeof(CgCtrl));
-    if (dense1 && host.pad) return mgp_fail(h, MGP_E_HIP, "dense CG: a hand-off inside the iteration kernel timed out");
-    if (!host.active || enq >= max_it) break;
-    long batch = check_every;
-    if (enq + batch > max_it) batch = max_it - enq;
-    if (dense1) {
-      for (long q = 0; q < batch; ++q, ++enq) MGP_TRY(mgp_dense1_step(h, &d1, enq + 1));
-      MGP_TRY(mgp_dense1_finish(h, &d1, rz, err_out, over));
-      continue;
-    }
-    for (long q = 0; q < batch; ++q, ++enq) {
-      const bool reset = (enq % cycle) == (cycle - 1);  // :71 (enq == state.i while active)
-      // dense operator + fused update: the skinny product may leave its slices for the update to add
-      const bool defer = !reset && fused_ept > 0 && op->kind == MGP_OP_DENSE && h->skinny_defer;
-      h->defer_slices = defer;
-      h->deferred_ks = 1;
-      h->defer_finish = !reset && fused_ept > 0 && op->kind == MGP_OP_SGPR && h->fuse_agree;
-      h->deferred_tt = nullptr;
-      const int rc_apply = apply_operator<T>(h, op, p, Bt, ap, &ctrl->active);
-      h->defer_slices = false;
-      h->defer_finish = false;
-      MGP_TRY(rc_apply);
-      if (!reset && fused_ept > 0) {
-        const T* dinv = pc.kind == MGP_PRE_JACOBI ? (const T*)pc.diag_inv : nullptr;
-        const T* ap_src = ap;
-        int ap_slices = 1;
-        long ap_stride = 0;
-        if (defer && h->deferred_ks > 1) {
-          ap_src = (const T*)h->deferred_part;
-          ap_slices = h->deferred_ks;
-          ap_stride = h->deferred_stride;
-        }
-        const T* agree = nullptr;
-        int world = 0;
-        if (h->deferred_tt != nullptr) {  // all-reduced partial left in place by the operator: [Bt, n] + word
-          ap_src = (const T*)h->deferred_tt;
-          agree = ap_src + tot;
-          world = h->deferred_world;
-        }
-#define MGP_FUSED(EPTV, NTV)                                                                                   \
-  hipLaunchKernelGGL((cg_update_fused_kernel<T, EPTV, NTV>), dim3((unsigned)Bt), dim3(NTV), 0, s, ctrl, V, r, p,    \
-                     ap_src, rz, over, err_out, n, (T)thr, (T)min_float, dinv, (int)max_it, ap_slices, ap_stride, agree, \
-                     world, coef, coef_steps)
-        switch (fused_ept) {
-          case 1: MGP_FUSED(1, 256); break;
-          case 2: MGP_FUSED(2, 256); break;
-          case 4: MGP_FUSED(4, 256); break;
-          case 14: MGP_FUSED(1, 1024); break;
-          case 12: MGP_FUSED(2, 1024); break;
-          case 24: MGP_FUSED(4, 1024); break;
-          default: MGP_FUSED(8, 1024); break;
-        }
-#undef MGP_FUSED
-        MGP_LAUNCH_CHECK(h);
-        continue;  // bookkeeping done inside the kernel
-      } else if (!reset) {
-        if (!dense_pre) {
-          MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 0, 0, coef, coef_steps);
-        } else {
-          MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 3, 0, coef, coef_steps);
-          MGP_LAUNCH_CHECK(h);
-          MGP_TRY(external_z(&ctrl->active));
-          MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                             over, err_out, n, (T)thr, (T)min_float, pc, 4, 0, coef, coef_steps);
-        }
-      } else {
-        MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                           over, err_out, n, (T)thr, (T)min_float, pc, 1, 0, (T*)nullptr, 0L);
-        MGP_LAUNCH_CHECK(h);
-        MGP_TRY(apply_operator<T>(h, op, V, Bt, ap, &ctrl->active));
-        hipLaunchKernelGGL((cg_residual_kernel<T>), dim3(nblk(tot)), dim3(256), 0, s, ctrl, B, ap, r, tot, 0);
-        MGP_LAUNCH_CHECK(h);
-        if (dense_pre) MGP_TRY(external_z(&ctrl->active));
-        MGP_UPDATE_LAUNCH(ctrl, V, r, p, z, ap, rz,
-                           over, err_out, n, (T)thr, (T)min_float, pc, dense_pre ? 5 : 2, 0, (T*)nullptr, 0L);
-      }
-      MGP_LAUNCH_CHECK(h);
-      hipLaunchKernelGGL(cg_advance_kernel, dim3(1), dim3(256), 0, s, ctrl, over, Bt, 1, (int)max_it);
-      MGP_LAUNCH_CHECK(h);
+
+  // every other route: poll, then enqueue the next batch while the device word says go on
+  int run_polled() {
+    for (;;) {
+      MGP_TRY(read_ctrl(h, a.ctrl, &host));
+      if (dense1 && host.pad) return mgp_fail(h, MGP_E_HIP, "dense CG: a hand-off inside the iteration kernel timed out");
+      if (!host.active || enq >= max_it) return MGP_OK;
+      MGP_TRY(enqueue_batch());
     }
   }
-  if (stats) {
+
+  int statistics(mgp_cg_stats* stats, std::chrono::steady_clock::time_point t0) {
+    if (!stats) return MGP_OK;
     stats->iterations = host.iters;
-    // converged iff the loop ended because no RHS was over threshold
-    int any = 0;
-    {
-      // `active` == 0 with iters < max_it means converged; at the cap, look at the flags
-      if (host.iters < max_it) {
-        any = 0;
-      } else {
-        std::string tmp;
-        tmp.resize((size_t)Bt * sizeof(int));
-        MGP_HIP(h, hipMemcpyAsync(&tmp[0], over, (size_t)Bt * sizeof(int), hipMemcpyDeviceToHost, s));
-        MGP_HIP(h, hipStreamSynchronize(s));
-        const int* f = (const int*)tmp.data();
-        for (long b = 0; b < Bt; ++b) any |= f[b];
-      }
+    int any = 0;  // converged iff no RHS is over threshold: `active` == 0 below the cap says so; at the cap, look at the flags
+    if (host.iters >= max_it) {
+      std::vector<int> f((size_t)Bt);
+      MGP_HIP(h, hipMemcpyAsync(f.data(), a.over, (size_t)Bt * sizeof(int), hipMemcpyDeviceToHost, s));
+      MGP_HIP(h, hipStreamSynchronize(s));
+      for (long b = 0; b < Bt; ++b) any |= f[b];
     }
     stats->converged = any ? 0 : 1;
     stats->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return MGP_OK;
   }
-#undef MGP_UPDATE_LAUNCH
-  return MGP_OK;
+};
+
+// decode the preconditioner, pick the routes, lay out the arena, start up, run one of three drivers, statistics
+template <typename T>
+int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const T* B, const T* V0, long Bt,
+                double thr, long max_it, long cycle, double min_float, int check_every, T* V, T* err_out,
+                mgp_cg_stats* stats, T* coef, long coef_steps, bool allow_persist) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const long n = op->n, tot = Bt * n;
+  PackHold pack_hold(h);  // the operator's X / Z / kernel are constant for the whole solve
+  CgPrecond pc;
+  MGP_TRY(decode_precond(h, pre, pc));
+  // Routes.  Up to d1_cols right-hand sides on a dense matrix, no residual refresh inside the solve: the tile scheme of
+  // cg_dense1.hip -- up to 8 where the full matrix fits the chip (n <= 2048: the register-resident form carries the
+  // columns for 16 fused multiply-adds each), else where it was measured faster than the skinny product: 4, 6 above 4096
+  const long d1_cols = h->cg_dense1_cols > 0 ? h->cg_dense1_cols
+                       : ((allow_persist && mgp_dense1_persist_eligible(h, n, 8))   ? 8
+                          : (allow_persist && mgp_dense1_persist_eligible(h, n, 6)) ? 6
+                                                                                    : (n <= 4096 ? 4 : 6));
+  const bool dense1 = op->kind == MGP_OP_DENSE && Bt >= 1 && Bt <= d1_cols && !pc.dense_pre &&
+                      pc.dev.kind != MGP_PRE_BLOCK && cycle > max_it && mgp_dense1_eligible(h, n) && coef == nullptr;
+  // n <= 4096: the whole solve in one launch, the upper triangle of A in registers (cg_dense1.hip)
+  const bool persist = dense1 && allow_persist && mgp_dense1_persist_eligible(h, n, Bt);
+  const bool fused = pc.dev.kind != MGP_PRE_BLOCK && !pc.dense_pre && Bt < 2147483647L && n <= kFusedMaxN;
+  MGP_TRY(mgp_reserve(h, &h->cg, &h->cg_bytes,
+                      CgArena<T>::bytes(tot, Bt, pc.need_z, dense1 ? mgp_dense1_bytes(h, op->dtype, n, Bt) : 0)));
+  const CgArena<T> arena(h->cg, tot, Bt, pc.need_z);
+  CgSolve<T> cg{h, op, B, /*Bt=*/Bt, /*n=*/n, /*tot=*/tot, /*max_it=*/max_it, /*cycle=*/cycle,
+                /*check_every=*/check_every < 1 ? 1L : (long)check_every, /*coef_steps=*/coef_steps,
+                /*thr=*/thr, /*min_float=*/min_float, /*V=*/V, /*err_out=*/err_out, /*coef=*/coef, /*s=*/h->stream,
+                /*pre=*/pc, /*a=*/arena, /*z=*/pc.cb ? (T*)pc.cb->cb_z : arena.z, /*dense1=*/dense1, /*fused=*/fused};
+  MGP_TRY(cg.start(V0, persist));
+  MGP_TRY(persist ? cg.run_persist() : (dense1 && h->poll_pipeline) ? cg.run_dense1_pipelined() : cg.run_polled());
+  return cg.statistics(stats, t0);
 }
-
-}  // namespace
-
-namespace {
 
 int pcg_solve_entry(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, const void* B, const void* V0,
                     int64_t Bt, double error_threshold, int64_t max_iterations, int64_t max_steps_cycle,
@@ -863,23 +896,21 @@ int pcg_solve_entry(mgp_handle* h, const mgp_operator* op, const mgp_precond* pr
   if (max_iterations < 0) return mgp_fail(h, MGP_E_BADARG, "max_iterations < 0");
   if (max_steps_cycle < 1) return mgp_fail(h, MGP_E_BADARG, "max_steps_cycle < 1");
   if (Bt > 2147483647L) return mgp_fail(h, MGP_E_SHAPE, "Bt too large");
-  auto run = [&]() -> int {
+  auto run = [&](bool allow_persist) -> int {
     return mgp_with_dtype(op->dtype, [&](auto t) {
       using T = decltype(t);
       return pcg_solve_t<T>(h, op, pre, (const T*)B, (const T*)V0, Bt, error_threshold, max_iterations, max_steps_cycle,
-                            min_float, check_every, (T*)V_out, (T*)err_out, stats, (T*)coef, coef_steps);
+                            min_float, check_every, (T*)V_out, (T*)err_out, stats, (T*)coef, coef_steps, allow_persist);
     });
   };
-  int rc = run();
+  int rc = run(true);
   if (rc == kRetryWithoutPersist) {
     if (V0 != nullptr && V0 == V_out)
       return mgp_fail(h, MGP_E_HIP, "dense CG: a hand-off between resident workgroups timed out (is the GPU shared?) and "
                                     "the initial solution was overwritten in place; set MGP_CG_DENSE1=1");
     fprintf(stderr, "libmgp: dense CG: a hand-off between resident workgroups timed out (is the GPU shared?); this solve "
                     "runs again with two launches per iteration\n");
-    h->d1_persist_off = true;  // the solve again, from its inputs, two launches per iteration
-    rc = run();
-    h->d1_persist_off = false;
+    rc = run(false);  // the solve again, from its inputs, two launches per iteration
   }
   return rc;
 }

@@ -1,6 +1,9 @@
-// cg_dense1.hip -- one right-hand side on a dense symmetric matrix: the reference's literal CG loop
-// (cggp/conjugate_gradient.py:59-98 with A = Kmm + Lambda, cggp/models.py:301-303,337-339) in TWO launches per
-// iteration, neither of which contains a hand-off between workgroups.
+// cg_dense1.hip -- one to eight right-hand sides on a dense symmetric matrix: the reference's literal CG loop
+// (cggp/conjugate_gradient.py:59-98 with A = Kmm + Lambda, cggp/models.py:301-303,337-339) in three forms, driven by
+// cg.hip through mgp_dense1_begin / _step / _persist_run / _finish (at the end): one right-hand side in TWO launches
+// per iteration, neither of which contains a hand-off between workgroups (d1_*_kernel, described next); two to eight
+// on the same two launches (d1m_*_kernel); and for n <= 4096 the whole solve in ONE launch with the matrix in registers
+// and bounded hand-offs between resident workgroups (d1_persist_*_kernel), failing over to the two-launch form.
 //
 //   iteration k (k = 1, 2, ...), the recurrence of conjugate_gradient.py:64-85:
 //       Ap = p_k A ; gamma = rz_{k-1} / (p_k . Ap) ; v += gamma p_k ; r -= gamma Ap ;

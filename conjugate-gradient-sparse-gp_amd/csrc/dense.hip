@@ -1166,7 +1166,8 @@ __global__ __launch_bounds__(256) void skinny_reduce_kernel(const T* __restrict_
 }
 
 template <typename T, int NBT>
-int symm_skinny_lds_launch(mgp_handle* h, const T* A, long n, const T* P, long Bt, T* out, const int* gate) {
+int symm_skinny_lds_launch(mgp_handle* h, const T* A, long n, const T* P, long Bt, T* out, const int* gate,
+                           MgpApLoc* loc) {
   constexpr int KW = (NBT * 16 * 64 * 2 * sizeof(T) <= 65536) ? 64 : 32;  // two staging buffers within 64 KB
   const long jg = (n + 63) / 64;
   // workgroups per CU: two for the narrow panels (Bt <= 32: 28-30 us instead of 33-35 at n = 4096), one for
@@ -1277,10 +1278,8 @@ int symm_skinny_lds_launch(mgp_handle* h, const T* A, long n, const T* P, long B
       }
     }
   }
-  if (ks > 1 && ks <= 8 && h->defer_slices) {  // the caller (the fused CG update) sums the slices as it reads them
-    h->deferred_part = dst;
-    h->deferred_ks = (int)ks;
-    h->deferred_stride = Bt * n;
+  if (ks > 1 && ks <= 8 && loc != nullptr) {  // the caller (the fused CG update) sums the slices as it reads them
+    *loc = MgpApLoc{dst, (int)ks, Bt * n, nullptr, 0};
     return MGP_OK;
   }
   if (ks > 1) {
@@ -1325,14 +1324,14 @@ int symm_gemv_tri_slots_t(mgp_handle* h, const T* A, long n, const T* P, const i
 }
 
 template <typename T>
-int symm_matmul_t(mgp_handle* h, const T* A, long n, const T* P, long Bt, T* out, const int* gate) {
+int symm_matmul_t(mgp_handle* h, const T* A, long n, const T* P, long Bt, T* out, const int* gate, MgpApLoc* loc) {
   if (Bt >= 2 && Bt <= 128) {
     const int nbt = Bt <= 16 ? 1 : (Bt <= 32 ? 2 : (Bt <= 64 ? 4 : 8));
     if (h->skinny_mode == 1) {  // P staged through LDS (default); MGP_SKINNY=reg selects the form below
-      if (nbt == 1) return symm_skinny_lds_launch<T, 1>(h, A, n, P, Bt, out, gate);
-      if (nbt == 2) return symm_skinny_lds_launch<T, 2>(h, A, n, P, Bt, out, gate);
-      if (nbt == 4) return symm_skinny_lds_launch<T, 4>(h, A, n, P, Bt, out, gate);
-      return symm_skinny_lds_launch<T, 8>(h, A, n, P, Bt, out, gate);
+      if (nbt == 1) return symm_skinny_lds_launch<T, 1>(h, A, n, P, Bt, out, gate, loc);
+      if (nbt == 2) return symm_skinny_lds_launch<T, 2>(h, A, n, P, Bt, out, gate, loc);
+      if (nbt == 4) return symm_skinny_lds_launch<T, 4>(h, A, n, P, Bt, out, gate, loc);
+      return symm_skinny_lds_launch<T, 8>(h, A, n, P, Bt, out, gate, loc);
     }
     const int BP = 16 * nbt;
     MGP_TRY(mgp_reserve(h, &h->ws, &h->ws_bytes, (size_t)n * BP * sizeof(T)));
@@ -1497,7 +1496,8 @@ int mgp_mirror_upper(mgp_handle* h, int dtype, void* out, const void* slices, in
 }
 
 int mgp_symm_matmul_gated(mgp_handle* h, int dtype, const void* A, int64_t n, const void* P, int64_t Bt,
-                          void* out, const int* gate) {
+                          void* out, const int* gate, MgpApLoc* loc) {
+  if (loc != nullptr) *loc = MgpApLoc{out, 1, 0, nullptr, 0};  // every form but the skinny product finishes into out
   if (!h) return MGP_E_BADARG;
   if (dtype != MGP_F32 && dtype != MGP_F64) return mgp_fail(h, MGP_E_DTYPE, "bad dtype %d", dtype);
   if (n < 0 || Bt < 0) return mgp_fail(h, MGP_E_SHAPE, "negative size");
@@ -1505,7 +1505,7 @@ int mgp_symm_matmul_gated(mgp_handle* h, int dtype, const void* A, int64_t n, co
   if (!A || !P || !out) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   return mgp_with_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    return symm_matmul_t<T>(h, (const T*)A, n, (const T*)P, Bt, (T*)out, gate);
+    return symm_matmul_t<T>(h, (const T*)A, n, (const T*)P, Bt, (T*)out, gate, loc);
   });
 }
 

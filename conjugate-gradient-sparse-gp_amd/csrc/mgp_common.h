@@ -81,7 +81,6 @@ struct mgp_handle {
   int d1_first_poll_sleep = 16;  // register-resident dense CG, owners: x 64 cycles before the first poll of the slots (MGP_D1_FIRST_POLL)
   int d1_inject_absent = -1;  // test only (MGP_D1_INJECT_ABSENT=<workgroup>): that workgroup of the register-resident solve leaves at once
   int d1_owner_spread = 1;  // super-block form, several columns: the columns of a chunk owned by different workgroups (MGP_D1_OWNER_SPREAD=0: by one)
-  bool d1_persist_off = false;  // set for the retry of a solve whose register-resident launch reported a timed-out hand-off
   int poll_pipeline = 1;  // MGP_CG_PIPELINE_POLLS=0: drain the stream at every poll (round 3)
   void* ones = nullptr;  // device constants: double 1.0 at +0, float 1.0f at +8
   void* e2tabs = nullptr;  // exp2 tables of the fast fp64 sweep (8192 + 2048 entries, sweep.hip: mgp_build_e2tabs)
@@ -126,20 +125,7 @@ struct mgp_handle {
   int gemm_ksplit = 1;  // mid-size GEMMs: 128x128 tiles x K slices instead of 64x64 tiles (MGP_GEMM_KSPLIT=0 disables)
   int skinny_blocks_per_cu = 0;  // k slices of the skinny product: workgroups per CU to aim for; 0 = by panel width (MGP_SKINNY_BPC)
   int skinny_stagger = 0;  // experiment (MGP_SKINNY_STAGGER): start-up delay units between workgroup phases
-  // Deferred slice sum of the skinny product (dense.hip -> cg.hip): while `defer_slices` is set the product leaves its
-  // contraction slices in `ws` instead of launching skinny_reduce_kernel and reports them here; the fused CG update
-  // adds them in slice order as it reads A.p (the same sums in the same order, one launch fewer per iteration).
-  bool defer_slices = false;
-  const void* deferred_part = nullptr;
-  int deferred_ks = 1;
-  long deferred_stride = 0;
-  // Deferred agreement check of the multi-rank SGPR operator (cg.hip): while `defer_finish` is set the operator
-  // leaves the all-reduced partial where the collective put it and reports it here; the fused CG update reads A.p
-  // from there and does finish_allreduce_kernel's test itself (agreement word == ranks, else the gate closes)
   int fuse_agree = 1;  // MGP_FUSE_AGREE=0: put_gate_word_kernel + finish_allreduce_kernel as launches of their own
-  bool defer_finish = false;
-  const void* deferred_tt = nullptr;
-  int deferred_world = 0;
   int skinny_defer = 1;  // MGP_SKINNY_DEFER=0 keeps the separate reduce launch inside the CG loop
   int skinny_pipe = 1;  // software-pipelined form of the LDS-staged product when n % 64 == 0 and Bt <= 64 (MGP_SKINNY_PIPE=0: the round-1 form)
   int skinny_mode = 1;  // 2 <= Bt <= 128 product: 1 = P staged through LDS, 0 = register operands (MGP_SKINNY=reg)
@@ -314,7 +300,19 @@ int mgp_build_e2tabs(mgp_handle* h);  // sweep.hip
 // Q[k][i] = contribution of chunk k to output element i, summed by the caller in k order
 int mgp_symm_gemv_tri_prepare(mgp_handle* h, int dtype, int64_t n, void** Q, const void** tab);
 
-// cg_dense1.hip: one right-hand side on a dense matrix, two launches per iteration
+// Where an operator form left A.p for the CG update (dense.hip, cg.hip): {out, 1, 0} when the product was finished into
+// the caller's `out`; 2..8 unreduced contraction slices of the skinny product, slice z at src + z * stride; or the
+// collective SGPR operator's all-reduced partial in place with the agreement word behind it (`agree`, compared with
+// `world`).  Only an entry point handed a non-null MgpApLoc* may leave A.p unfinished; the handle carries no per-call state.
+struct MgpApLoc {
+  const void* src;
+  int slices;
+  long stride;
+  const void* agree;
+  int world;
+};
+
+// cg_dense1.hip: up to eight right-hand sides on a dense matrix, two launches per iteration or (n <= 4096) one per solve
 struct MgpCgCtrl {
   int active;
   int iters;
@@ -424,7 +422,7 @@ int mgp_symm_gemv_rows_acc(mgp_handle* h, int dtype, const void* A, int64_t n, c
 // comm.hip: the operator's all-reduce on the handle's stream (errors land in the handle)
 int mgp_comm_allreduce_on(mgp_handle* h, mgp_comm* comm, void* buf, size_t count, int dtype);
 int mgp_symm_matmul_gated(mgp_handle* h, int dtype, const void* A, int64_t n, const void* P, int64_t Bt,
-                          void* out, const int* gate);
+                          void* out, const int* gate, MgpApLoc* loc = nullptr);
 // pivchol.hip: Z[Bt, n] = diag_inv o R - (R B^T) B, B [k, n]; gate: device int, skip if 0
 int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
                             const void* R, int64_t Bt, void* Z, const int* gate);
