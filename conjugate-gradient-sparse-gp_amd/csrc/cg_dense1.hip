@@ -1,284 +1,44 @@
 // cg_dense1.hip -- one to eight right-hand sides on a dense symmetric matrix: the reference's literal CG loop
-// (cggp/conjugate_gradient.py:59-98 with A = Kmm + Lambda, cggp/models.py:301-303,337-339) in three forms, driven by
-// cg.hip through mgp_dense1_begin / _step / _persist_run / _finish (at the end): one right-hand side in TWO launches
-// per iteration, neither of which contains a hand-off between workgroups (d1_*_kernel, described next); two to eight
-// on the same two launches (d1m_*_kernel); and for n <= 4096 the whole solve in ONE launch with the matrix in registers
-// and bounded hand-offs between resident workgroups (d1_persist_*_kernel), failing over to the two-launch form.
+// (cggp/conjugate_gradient.py:59-98 with A = Kmm + Lambda, cggp/models.py:301-303,337-339) in two forms, driven by
+// cg.hip through mgp_dense1_begin / _step / _persist_run / _finish (at the end): TWO launches per iteration, neither
+// of which contains a hand-off between workgroups (d1_init / d1_finish / d1_tile / d1_update_kernel, one family for
+// 1 .. 8 columns, described next); and for n <= 4096 the whole solve in ONE launch with the matrix in registers and
+// bounded hand-offs between resident workgroups (d1_persist_*_kernel), failing over to the two-launch form.
 //
-//   iteration k (k = 1, 2, ...), the recurrence of conjugate_gradient.py:64-85:
+//   iteration k (k = 1, 2, ...), the recurrence of conjugate_gradient.py:64-85, per column:
 //       Ap = p_k A ; gamma = rz_{k-1} / (p_k . Ap) ; v += gamma p_k ; r -= gamma Ap ;
 //       z = M^-1 r ; rz_k = z . r ; p_{k+1} = z + (rz_k / rz_{k-1}) p_k
 //
-//   T_k  tile kernel, one workgroup per 64x64 tile of the upper triangle (A is read once, n^2/2 elements):
+//   T_k  tile kernel, one workgroup per 64x64 tile of the upper triangle (A is read once, n^2/2 elements, whatever
+//        the number of columns BT), and per column:
 //          - every workgroup adds the per-chunk shares of rz_{k-1} and ||r||^2 that U_{k-1} left (64 numbers, the
-//            same fixed-order sum everywhere), applies the stopping rule (:59-62) and forms beta;
+//            same fixed-order sum everywhere), applies the stopping rule (:59-62, the reference's `any` over the
+//            columns) and forms beta;
 //          - forms the entries of p_k it needs ON THE FLY, p_k = z + beta p_{k-1} (:77-84) -- the direction is never
 //            a separate pass; the diagonal tiles store p_k for U_k and T_{k+1};
-//          - tile products A_IJ p_J and A_IJ^T p_I into their slots (dense.hip's upper-triangle product), and the
-//            tile's share of p_k . A p_k  (= p_I . (A_IJ p_J), twice for I < J).
-//   U_k  update kernel, one workgroup per 64-element chunk, chunk-local: adds the 2080 tile shares (the same
-//        fixed-order sum everywhere) -> gamma (:66-68); adds its chunk's slots -> Ap; v, r (:69,76); z; its shares of
-//        rz_k and ||r||^2.
+//          - tile products A_IJ p_J and A_IJ^T p_I into their slots Q[column][chunk][n] (dense.hip's upper-triangle
+//            product), and the tile's share of p_k . A p_k  (= p_I . (A_IJ p_J), twice for I < J).
+//   U_k  update kernel, one workgroup per (64-element chunk, column), chunk-local: adds the column's 2080 tile shares
+//        (the same fixed-order sum everywhere) -> gamma (:66-68); adds its chunk's slots -> Ap; v, r (:69,76); z; its
+//        shares of rz_k and ||r||^2.
 //
 // Every global scalar of the recurrence is therefore produced by one launch and consumed by the NEXT one: the
 // launch boundary is the only synchronisation.  Round 2 ran tile kernel + slot-reduce launch + a one-workgroup
 // update launch (14.0 + 4.6 + 7.1 us at n = 4096); a single launch for slot sums and update with an arrival ticket
 // measured 9.2 us, all of it dependent round trips (slots -> write-through publication -> ticket -> re-read ->
-// two block reductions).  All sums are in fixed order: results are run-to-run identical.
+// two block reductions).  All sums are in fixed order: results are run-to-run identical, and a column's iterate
+// does not depend on how many columns ride along.
 #include "mgp_common.h"
 
 namespace {
 
 constexpr int CP = 128;  // per-chunk shares: n <= 8192
 
-template <typename T>
-__device__ __forceinline__ T wave_allsum(T v) {
-  // xor butterfly: paired lanes add the same two numbers (a + b == b + a), so every lane ends with the same bits
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-template <typename T, int HALF, int BIT>
-__device__ __forceinline__ void rs_step(T (&x)[16], int l) {  // see dense.hip: lane_reduce_scatter_step
-  const bool hi = (l & BIT) != 0;
-#pragma unroll
-  for (int k = 0; k < HALF; ++k) {
-    const T keep = hi ? x[k + HALF] : x[k];
-    const T send = hi ? x[k] : x[k + HALF];
-    x[k] = keep + __shfl_xor(send, BIT, 64);
-  }
-}
-
-// rz and ||r||^2 of the current residual from the per-chunk shares: the same arithmetic in T, U's host finish
-// and nowhere else, so every consumer sees the same bits
-template <typename T>
-__device__ __forceinline__ void sum_shares(const T* __restrict__ cpart, int l, T& rz, T& rr) {
-  // all 2 CP entries exist; those of chunks beyond nt were zeroed by mgp_dense1_begin
-  rz = wave_allsum(cpart[l] + cpart[64 + l]);
-  rr = wave_allsum(cpart[CP + l] + cpart[CP + 64 + l]);
-}
-
-// r = b - av ; z ; shares of rz_0 and ||r_0||^2 ; scal[1] = 0 makes T_1 take p_1 = z_0 (the beta-term dropped)
-template <typename T>
-__global__ __launch_bounds__(64) void d1_init_kernel(MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ b,
-                                                     const T* __restrict__ av, T* __restrict__ r,
-                                                     const T* __restrict__ dinv, T* __restrict__ cpart,
-                                                     T* __restrict__ scal, T* __restrict__ zpub, long n) {
-  const int l = threadIdx.x;
-  const long i = (long)blockIdx.x * 64 + l;
-  T rv = 0, zv = 0;
-  if (i < n) {
-    rv = av ? b[i] - av[i] : b[i];
-    r[i] = rv;
-    zv = dinv ? rv * dinv[i] : rv;
-    zpub[i] = zv;  // z_0 for the register-resident form
-  }
-  const T prz = wave_allsum(zv * rv), prr = wave_allsum(rv * rv);
-  if (l == 0) {
-    cpart[blockIdx.x] = prz;
-    cpart[CP + blockIdx.x] = prr;
-    if (blockIdx.x == 0) {
-      scal[0] = 0;
-      scal[1] = 0;
-      ctrl->active = 1;
-      ctrl->iters = 0;
-      ctrl->ticket = 0;
-      ctrl->pad = 0;
-    }
-  }
-}
-
-// statistics + gate for the host poll (once per enqueued batch)
-template <typename T>
-__global__ __launch_bounds__(64) void d1_finish_kernel(MgpCgCtrl* __restrict__ ctrl, const int* __restrict__ hand_off_err,
-                                                       const T* __restrict__ cpart, T* __restrict__ rz,
-                                                       T* __restrict__ err, int* __restrict__ over, T thr, int max_it) {
-  T s_rz, s_rr;
-  sum_shares(cpart, (int)threadIdx.x, s_rz, s_rr);
-  if (threadIdx.x == 0) {
-    rz[0] = s_rz;
-    err[0] = (T)0.5 * s_rz;
-    const int any = ((T)0.5 * s_rr > thr) ? 1 : 0;
-    over[0] = any;
-    if (*hand_off_err) ctrl->pad = 1;  // the register-resident form ran out of a poll budget
-    if (ctrl->active) ctrl->active = (any && ctrl->iters < max_it && !*hand_off_err) ? 1 : 0;
-  }
-}
-
-template <typename T, bool JAC>
-__global__ __launch_bounds__(256) void d1_tile_kernel(const MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ A, long n,
-                                                      const T* __restrict__ r, const T* __restrict__ dinv,
-                                                      const T* __restrict__ p_old, T* __restrict__ p_new,
-                                                      const T* __restrict__ cpart, T* __restrict__ scal, int k,
-                                                      const int2* __restrict__ tab, T* __restrict__ Q,
-                                                      T* __restrict__ tpart, T thr, T min_float, int max_it,
-                                                      int* __restrict__ stopw) {
-  // Gate: `active` is written by finish kernels only, stopw[(k-1) & 1] by the tile kernel of the PREVIOUS iteration --
-  // nothing this launch writes (ADVICE r3: block 0 used to clear ctrl->active while other workgroups of the same
-  // launch read it at entry).  A shut launch hands the shut on, so every later launch of the batch stays shut.
-  if (ctrl->active == 0 || stopw[(k + 1) & 1] != 0) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) stopw[k & 1] = 1;
-    return;
-  }
-  constexpr int TS = 64;
-  __shared__ T colp[4][TS];
-  __shared__ T wsum[4];
-  const int t = threadIdx.x, l = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const long b = blockIdx.x;
-  const int2 ij = tab[b];  // uniform: a scalar load
-  const int I = ij.x, J = ij.y;
-  const long r0 = (long)I * TS + 16 * w, c = (long)J * TS + l, ci = (long)I * TS + l;
-  // Issue order matters: vmcnt retires in order, so whatever is requested BEHIND the tile cannot be used before
-  // the tile has landed.  The operands of the recurrence (L2-resident, ten loads) go first, the 16 tile loads
-  // behind them, and beta and p_k are formed while the tile is in flight.  No branch anywhere between the loads
-  // and their uses -- ragged edges by clamped addresses and selects, the Jacobi diagonal by a template parameter,
-  // a converged solve runs this kernel once more with its stores switched off: the compiler sinks a load into the
-  // conditional block that uses it, and at a join of two paths its wait counts are the pessimistic merge (the
-  // first version waited for 12 of the 16 tile loads before it touched the shares).
-  const T z0 = cpart[l], z1 = cpart[64 + l], q0 = cpart[CP + l], q1 = cpart[CP + 64 + l];
-  const long cj = c < n ? c : n - 1, cic = ci < n ? ci : n - 1;
-  const T rj = r[cj], poj = p_old[cj], ri = r[cic], poi = p_old[cic];
-  const T dj = JAC ? dinv[cj] : (T)1, di = JAC ? dinv[cic] : (T)1;
-  const T rz_old = scal[k & 1];
-  const int it = ctrl->iters;
-  __builtin_amdgcn_sched_barrier(0);
-  T a[16];
-  {
-    // row q of the wave's 16: one pointer bump per row, frozen at the last row of the matrix (no 64-bit multiply
-    // per load)
-    const T* row = A + (r0 < n ? r0 : n - 1) * n + cj;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      a[q] = *row;
-      row += (r0 + q + 1 < n) ? n : 0;
-    }
-  }
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int q = 0; q < 16; ++q) a[q] = (r0 + q < n && c < n) ? a[q] : (T)0;
-  const T rz_new = wave_allsum(z0 + z1), rr_new = wave_allsum(q0 + q1);
-  // the stopping rule (:59-62): the same decision in every workgroup; `live` switches the stores off
-  const bool live = (T)0.5 * rr_new > thr && it < max_it;
-  if (b == 0 && t == 0) {
-    if (live) scal[(k + 1) & 1] = rz_new;  // U_k's numerator of gamma, T_{k+1}'s rz_old
-    stopw[k & 1] = live ? 0 : 1;           // read by U_k and T_{k+1}, one launch later each
-  }
-  const bool drop = rz_old <= min_float;  // :79; also how the first direction p_1 = z_0 comes out
-  const T beta = drop ? (T)0 : rz_new / rz_old;
-  const T zj = JAC ? rj * dj : rj, zi = JAC ? ri * di : ri;
-  T pj = drop ? zj : mgp_fma(beta, poj, zj);  // a select, not 0 * p_old: the arena may hold anything at start-up
-  T pi = drop ? zi : mgp_fma(beta, poi, zi);
-  pj = c < n ? pj : (T)0;
-  pi = ci < n ? pi : (T)0;
-  if (live && I == J && w == 0 && c < n) p_new[c] = pj;
-  T x[16];
-  T cs = 0;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    x[q] = a[q] * pj;
-    cs = mgp_fma(a[q], mgp_read_lane(pi, 16 * w + q), cs);
-  }
-  colp[w][l] = cs;
-  rs_step<T, 8, 32>(x, l);
-  rs_step<T, 4, 16>(x, l);
-  rs_step<T, 2, 8>(x, l);
-  rs_step<T, 1, 4>(x, l);
-  T s = x[0];
-  s += __shfl_xor(s, 2, 64);
-  s += __shfl_xor(s, 1, 64);  // lane l: (A_IJ p_J)[16 w + (l >> 2)]
-  const long i = r0 + (l >> 2);
-  if (live && (l & 3) == 0 && i < n) Q[(long)J * n + i] = s;
-  // the tile's share of p . A p: rows of this wave, then the four waves in order
-  const T prow = __shfl(pi, 16 * w + (l >> 2), 64);
-  const T u = wave_allsum((l & 3) == 0 ? s * prow : (T)0);
-  if (l == 0) wsum[w] = u;
-  __syncthreads();
-  if (live && t < TS && I != J) {
-    const T sc = (colp[0][t] + colp[1][t]) + (colp[2][t] + colp[3][t]);
-    const long ic2 = (long)J * TS + t;
-    if (ic2 < n) Q[(long)I * n + ic2] = sc;
-  }
-  if (live && t == 0) {
-    const T tot = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-    tpart[b] = I == J ? tot : tot + tot;
-  }
-}
-
-template <typename T, bool JAC, int NT, int PER, int TPM>
-__global__ __launch_bounds__(NT) void d1_update_kernel(MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ Q, int nt,
-                                                       const T* __restrict__ tpart, long ntiles,
-                                                       const T* __restrict__ scal, int k, const T* __restrict__ p,
-                                                       T* __restrict__ v, T* __restrict__ r,
-                                                       const T* __restrict__ dinv, T* __restrict__ cpart, long n,
-                                                       T min_float, const int* __restrict__ stopw) {
-  if (ctrl->active == 0 || stopw[k & 1] != 0) return;  // T_k (the previous launch) found the solve finished
-  constexpr int NW = NT / 64;
-  __shared__ T part[NW][64];
-  __shared__ T red[NW];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const long c = blockIdx.x;
-  const long i = c * 64 + lane;
-  const long ic = i < n ? i : n - 1;
-  // every load of the kernel is issued here, clamped instead of guarded
-  const int kb = wave * PER;
-  T sl[PER];
-#pragma unroll
-  for (int q = 0; q < PER; ++q) {
-    const int kk = kb + q < nt ? kb + q : nt - 1;
-    sl[q] = Q[(long)kk * n + ic];
-  }
-  T tp[TPM];
-#pragma unroll
-  for (int m = 0; m < TPM; ++m) {
-    const long e = (long)m * NT + t;
-    tp[m] = tpart[e < ntiles ? e : ntiles - 1];
-  }
-  const T pc = p[ic], rc = r[ic], vc = v[ic];
-  const T dc = JAC ? dinv[ic] : (T)1;
-  const T rz_prev = scal[(k + 1) & 1];
-  // p . A p: thread-sequential over its shares, lanes by butterfly, waves in order -- the same bits in every workgroup
-  T d = 0;
-#pragma unroll
-  for (int m = 0; m < TPM; ++m) d += ((long)m * NT + t < ntiles) ? tp[m] : (T)0;
-  d = wave_allsum(d);
-  if (lane == 0) red[wave] = d;
-  T s = 0;
-#pragma unroll
-  for (int q = 0; q < PER; ++q) s += (kb + q < nt) ? sl[q] : (T)0;
-  part[wave][lane] = s;
-  __syncthreads();
-  if (wave != 0) return;
-  d = red[0];
-#pragma unroll
-  for (int q = 1; q < NW; ++q) d += red[q];
-  const T gamma = (d <= min_float) ? (T)0 : rz_prev / d;  // :66-68
-  T a = part[0][lane];
-#pragma unroll
-  for (int q = 1; q < NW; ++q) a += part[q][lane];
-  const T vn = mgp_fma(gamma, pc, vc);   // :69
-  const T rn = mgp_fma(-gamma, a, rc);   // :76
-  const T zn = JAC ? rn * dc : rn;       // :77
-  const bool ok = i < n;
-  if (ok) {
-    v[i] = vn;
-    r[i] = rn;
-  }
-  const T prz = wave_allsum(ok ? zn * rn : (T)0), prr = wave_allsum(ok ? rn * rn : (T)0);
-  if (lane == 0) {
-    cpart[c] = prz;
-    cpart[CP + c] = prr;
-    if (c == 0) ctrl->iters = ctrl->iters + 1;
-  }
-}
-
-// write-through store / L1-bypassing load of one element (global_store/load ... sc1): the two halves of a hand-off
-// between resident workgroups without fences (MI355X_MICROARCH.md, hand-off table)
-// ---- cross-lane moves on the vector ALU (gfx950): `__shfl_xor` lowers to ds_bpermute -- the LDS crossbar, ~100
-// cycles of latency per dependent step -- which the tile kernels above hide behind seven workgroups per CU; the
-// register-resident kernel runs three waves per SIMD, so its reduction chains use DPP (within a row of 16 lanes) and
-// v_permlane16_swap / v_permlane32_swap (between rows / halves) instead.
+// ---- cross-lane moves on the vector ALU (gfx950): `__shfl_xor` (mgp_wave_sum) lowers to ds_bpermute -- the LDS
+// crossbar, ~100 cycles of latency per dependent step.  The init, finish and update kernels have one or two such
+// chains and keep it; the tile kernel (72 steps per column) and the register-resident kernels (three waves per SIMD
+// to hide them behind) use DPP (within a row of 16 lanes) and v_permlane16_swap / v_permlane32_swap (between rows /
+// halves) instead.  Both forms add the same pairs, so the bits are the same.
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov(double v) {
   const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xF, 0xF, true);
@@ -357,20 +117,33 @@ __device__ __forceinline__ void rs_step_row(T (&x)[16], int l) {
   }
 }
 
-// ------------------------------------------------------------------ round 4: 2 .. 8 right-hand sides on the tile scheme
+// ------------------------------------------------------------------ two launches per iteration, 1 .. 8 right-hand sides
 // The reference's default probe count is 5 (`CGGP(num_probes=5)`, cggp/models.py:286): every `prior_kl` and
-// `eval_logdet` of a training step is a 5-column CG on Kmm + Lambda.  Round 3 ran those through the skinny MFMA
-// product (the whole matrix read, a third of the matrix cores' columns used) + the fused update: 35 us per iteration
-// at n = 4096.  Here the two-launch iteration above carries BT columns: T reads each upper-triangle tile ONCE and
-// forms, per column, the direction on the fly, both tile products and the share of p.Ap; U -- one workgroup per
-// (chunk, column) -- is d1_update_kernel with a column index.  Same recurrence per column (:64-85), the reference's
-// `any` over the columns as stopping rule (:59-62), the same guards per column (:68, :79), sums in fixed order.
+// `eval_logdet` of a training step is a 5-column CG on Kmm + Lambda, beside the one-column solve of `predict_f`.
+// Round 3 ran the several-column ones through the skinny MFMA product (the whole matrix read, a third of the matrix
+// cores' columns used) + the fused update: 35 us per iteration at n = 4096.  Here one kernel family carries BT
+// columns: T reads each upper-triangle tile ONCE and forms, per column, the direction on the fly, both tile products
+// and the share of p.Ap; U runs one workgroup per (chunk, column = blockIdx.y).  Same recurrence per column (:64-85),
+// the reference's `any` over the columns as stopping rule (:59-62), the same guards per column (:68, :79), sums in
+// fixed order.  Arena per column e: r, v, p, zpub at e n; cpart at e 2 CP; scal at 2 e; tpart at e ntiles; slots at
+// Q[(e nt + chunk) n + i].
+
+// rz and ||r||^2 of the current residual from a column's per-chunk shares: the same arithmetic in T, the finish
+// kernel and nowhere else, so every consumer sees the same bits
 template <typename T>
-__global__ __launch_bounds__(64) void d1m_init_kernel(MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ b,
-                                                      const T* __restrict__ av, T* __restrict__ r,
-                                                      const T* __restrict__ dinv, T* __restrict__ cpart,
-                                                      T* __restrict__ scal, T* __restrict__ zpub, long n,
-                                                      int* __restrict__ stopw) {
+__device__ __forceinline__ void sum_shares(const T* __restrict__ cpart, int l, T& rz, T& rr) {
+  // all 2 CP entries exist; those of chunks beyond nt were zeroed by mgp_dense1_begin
+  rz = mgp_wave_sum(cpart[l] + cpart[64 + l]);
+  rr = mgp_wave_sum(cpart[CP + l] + cpart[CP + 64 + l]);
+}
+
+// r = b - av ; z ; shares of rz_0 and ||r_0||^2 ; scal = 0 makes T_1 take p_1 = z_0 (the beta-term dropped).  The two
+// stop words are zero already: mgp_dense1_begin clears their line on the same stream before this launch.
+template <typename T>
+__global__ __launch_bounds__(64) void d1_init_kernel(MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ b,
+                                                     const T* __restrict__ av, T* __restrict__ r,
+                                                     const T* __restrict__ dinv, T* __restrict__ cpart,
+                                                     T* __restrict__ scal, T* __restrict__ zpub, long n) {
   const int l = threadIdx.x, col = blockIdx.y;
   const long i = (long)blockIdx.x * 64 + l, off = (long)col * n;
   T rv = 0, zv = 0;
@@ -380,7 +153,7 @@ __global__ __launch_bounds__(64) void d1m_init_kernel(MgpCgCtrl* __restrict__ ct
     zv = dinv ? rv * dinv[i] : rv;
     zpub[off + i] = zv;  // z_0 for the register-resident form
   }
-  const T prz = wave_allsum(zv * rv), prr = wave_allsum(rv * rv);
+  const T prz = mgp_wave_sum(zv * rv), prr = mgp_wave_sum(rv * rv);
   if (l == 0) {
     T* cp = cpart + (long)col * 2 * CP;
     cp[blockIdx.x] = prz;
@@ -393,20 +166,18 @@ __global__ __launch_bounds__(64) void d1m_init_kernel(MgpCgCtrl* __restrict__ ct
         ctrl->iters = 0;
         ctrl->ticket = 0;
         ctrl->pad = 0;
-        stopw[0] = 0;
-        stopw[1] = 0;
       }
     }
   }
 }
 
-// statistics per column + the gate for the host poll: one wave per column
+// statistics per column + the gate for the host poll (once per enqueued batch): one wave per column
 template <typename T>
-__global__ __launch_bounds__(512) void d1m_finish_kernel(MgpCgCtrl* __restrict__ ctrl,
-                                                         const int* __restrict__ hand_off_err,
-                                                         const T* __restrict__ cpart, T* __restrict__ rz,
-                                                         T* __restrict__ err, int* __restrict__ over, T thr,
-                                                         int max_it, int bt) {
+__global__ __launch_bounds__(512) void d1_finish_kernel(MgpCgCtrl* __restrict__ ctrl,
+                                                        const int* __restrict__ hand_off_err,
+                                                        const T* __restrict__ cpart, T* __restrict__ rz,
+                                                        T* __restrict__ err, int* __restrict__ over, T thr,
+                                                        int max_it, int bt) {
   __shared__ int any_s[8];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   if (w < bt) {
@@ -430,14 +201,17 @@ __global__ __launch_bounds__(512) void d1m_finish_kernel(MgpCgCtrl* __restrict__
 }
 
 template <typename T, bool JAC, int BT>
-__global__ __launch_bounds__(256) void d1m_tile_kernel(const MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ A,
-                                                       long n, const T* __restrict__ r, const T* __restrict__ dinv,
-                                                       const T* __restrict__ p_old, T* __restrict__ p_new,
-                                                       const T* __restrict__ cpart, T* __restrict__ scal, int k,
-                                                       const int2* __restrict__ tab, T* __restrict__ Q, int nt,
-                                                       T* __restrict__ tpart, long ntiles, T thr, T min_float,
-                                                       int max_it, int* __restrict__ stopw) {
-  if (ctrl->active == 0 || stopw[(k + 1) & 1] != 0) {  // see d1_tile_kernel
+__global__ __launch_bounds__(256) void d1_tile_kernel(const MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ A,
+                                                      long n, const T* __restrict__ r, const T* __restrict__ dinv,
+                                                      const T* __restrict__ p_old, T* __restrict__ p_new,
+                                                      const T* __restrict__ cpart, T* __restrict__ scal, int k,
+                                                      const int2* __restrict__ tab, T* __restrict__ Q, int nt,
+                                                      T* __restrict__ tpart, long ntiles, T thr, T min_float,
+                                                      int max_it, int* __restrict__ stopw) {
+  // Gate: `active` is written by finish kernels only, stopw[(k-1) & 1] by the tile kernel of the PREVIOUS iteration --
+  // nothing this launch writes (ADVICE r3: block 0 used to clear ctrl->active while other workgroups of the same
+  // launch read it at entry).  A shut launch hands the shut on, so every later launch of the batch stays shut.
+  if (ctrl->active == 0 || stopw[(k + 1) & 1] != 0) {
     if (blockIdx.x == 0 && threadIdx.x == 0) stopw[k & 1] = 1;
     return;
   }
@@ -447,11 +221,17 @@ __global__ __launch_bounds__(256) void d1m_tile_kernel(const MgpCgCtrl* __restri
   const int t = threadIdx.x, l = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const long b = blockIdx.x;
-  const int2 ij = tab[b];
+  const int2 ij = tab[b];  // uniform: a scalar load
   const int I = ij.x, J = ij.y;
   const long r0 = (long)I * TS + 16 * w, c = (long)J * TS + l, ci = (long)I * TS + l;
   const long cj = c < n ? c : n - 1, cic = ci < n ? ci : n - 1;
-  // the recurrence's operands of every column first (L2-resident), the tile's 16 loads behind them (d1_tile_kernel)
+  // Issue order matters: vmcnt retires in order, so whatever is requested BEHIND the tile cannot be used before
+  // the tile has landed.  The operands of the recurrence (L2-resident, ten loads per column) go first, the 16 tile
+  // loads behind them, and beta and p_k are formed while the tile is in flight.  No branch anywhere between the
+  // loads and their uses -- ragged edges by clamped addresses and selects, the Jacobi diagonal by a template
+  // parameter, a converged solve runs this kernel once more with its stores switched off: the compiler sinks a load
+  // into the conditional block that uses it, and at a join of two paths its wait counts are the pessimistic merge
+  // (the first version waited for 12 of the 16 tile loads before it touched the shares).
   T z0[BT], z1[BT], q0[BT], q1[BT], rj[BT], poj[BT], ri[BT], poi[BT], rzo[BT];
 #pragma unroll
   for (int e = 0; e < BT; ++e) {
@@ -466,6 +246,8 @@ __global__ __launch_bounds__(256) void d1m_tile_kernel(const MgpCgCtrl* __restri
   __builtin_amdgcn_sched_barrier(0);
   T a[16];
   {
+    // row q of the wave's 16: one pointer bump per row, frozen at the last row of the matrix (no 64-bit multiply
+    // per load)
     const T* row = A + (r0 < n ? r0 : n - 1) * n + cj;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -479,19 +261,21 @@ __global__ __launch_bounds__(256) void d1m_tile_kernel(const MgpCgCtrl* __restri
   bool any = false;
 #pragma unroll
   for (int e = 0; e < BT; ++e) {
-    rzn[e] = wave_allsum_valu(z0[e] + z1[e]);  // the same bits as wave_allsum (commutative butterfly)
+    rzn[e] = wave_allsum_valu(z0[e] + z1[e]);  // the same bits as sum_shares (commutative butterfly)
     const T rr_new = wave_allsum_valu(q0[e] + q1[e]);
     any = any || (T)0.5 * rr_new > thr;
   }
-  const bool live = any && it < max_it;  // :59-62: `any` over the columns
-  if (b == 0 && t == 0) stopw[k & 1] = live ? 0 : 1;
+  // the stopping rule (:59-62, `any` over the columns): the same decision in every workgroup; `live` switches the
+  // stores off
+  const bool live = any && it < max_it;
+  if (b == 0 && t == 0) stopw[k & 1] = live ? 0 : 1;  // read by U_k and T_{k+1}, one launch later each
 #pragma unroll
   for (int e = 0; e < BT; ++e) {
-    if (b == 0 && t == 0 && live) scal[2 * e + ((k + 1) & 1)] = rzn[e];
-    const bool drop = rzo[e] <= min_float;  // :79, per column
+    if (b == 0 && t == 0 && live) scal[2 * e + ((k + 1) & 1)] = rzn[e];  // U_k's numerator of gamma, T_{k+1}'s rz_old
+    const bool drop = rzo[e] <= min_float;  // :79, per column; also how the first direction p_1 = z_0 comes out
     const T beta = drop ? (T)0 : rzn[e] / rzo[e];
     const T zj = JAC ? rj[e] * dj : rj[e], zi = JAC ? ri[e] * di : ri[e];
-    T vj = drop ? zj : mgp_fma(beta, poj[e], zj);
+    T vj = drop ? zj : mgp_fma(beta, poj[e], zj);  // a select, not 0 * p_old: the arena may hold anything at start-up
     T vi = drop ? zi : mgp_fma(beta, poi[e], zi);
     pj[e] = c < n ? vj : (T)0;
     pi[e] = ci < n ? vi : (T)0;
@@ -523,6 +307,7 @@ __global__ __launch_bounds__(256) void d1m_tile_kernel(const MgpCgCtrl* __restri
     s += lane_xor_row<1>(s);  // lane l: (A_IJ p_J)[16 w + (l >> 2)]
     const long i = r0 + (l >> 2);
     if (live && (l & 3) == 0 && i < n) Q[((long)e * nt + J) * n + i] = s;
+    // the tile's share of p . A p: rows of this wave, then the four waves in order
     const T prow = __shfl(pi[e], 16 * w + (l >> 2), 64);
     const T u = wave_allsum_valu((l & 3) == 0 ? s * prow : (T)0);
     if (l == 0) wsum[e][w] = u;
@@ -543,15 +328,14 @@ __global__ __launch_bounds__(256) void d1m_tile_kernel(const MgpCgCtrl* __restri
   }
 }
 
-// U for column blockIdx.y: d1_update_kernel's arithmetic on that column's slots, shares and vectors
 template <typename T, bool JAC, int NT, int PER, int TPM>
-__global__ __launch_bounds__(NT) void d1m_update_kernel(MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ Q, int nt,
-                                                        const T* __restrict__ tpart, long ntiles,
-                                                        const T* __restrict__ scal, int k, const T* __restrict__ p,
-                                                        T* __restrict__ v, T* __restrict__ r,
-                                                        const T* __restrict__ dinv, T* __restrict__ cpart, long n,
-                                                        T min_float, const int* __restrict__ stopw) {
-  if (ctrl->active == 0 || stopw[k & 1] != 0) return;
+__global__ __launch_bounds__(NT) void d1_update_kernel(MgpCgCtrl* __restrict__ ctrl, const T* __restrict__ Q, int nt,
+                                                       const T* __restrict__ tpart, long ntiles,
+                                                       const T* __restrict__ scal, int k, const T* __restrict__ p,
+                                                       T* __restrict__ v, T* __restrict__ r,
+                                                       const T* __restrict__ dinv, T* __restrict__ cpart, long n,
+                                                       T min_float, const int* __restrict__ stopw) {
+  if (ctrl->active == 0 || stopw[k & 1] != 0) return;  // T_k (the previous launch) found the solve finished
   constexpr int NW = NT / 64;
   __shared__ T part[NW][64];
   __shared__ T red[NW];
@@ -561,6 +345,7 @@ __global__ __launch_bounds__(NT) void d1m_update_kernel(MgpCgCtrl* __restrict__ 
   const long ic = i < n ? i : n - 1;
   const T* Qc = Q + (long)col * nt * n;
   const T* tpc = tpart + (long)col * ntiles;
+  // every load of the kernel is issued here, clamped instead of guarded
   const int kb = wave * PER;
   T sl[PER];
 #pragma unroll
@@ -577,10 +362,11 @@ __global__ __launch_bounds__(NT) void d1m_update_kernel(MgpCgCtrl* __restrict__ 
   const T pc = p[off + ic], rc = r[off + ic], vc = v[off + ic];
   const T dc = JAC ? dinv[ic] : (T)1;
   const T rz_prev = scal[2 * col + ((k + 1) & 1)];
+  // p . A p: thread-sequential over its shares, lanes by butterfly, waves in order -- the same bits in every workgroup
   T d = 0;
 #pragma unroll
   for (int m = 0; m < TPM; ++m) d += ((long)m * NT + t < ntiles) ? tp[m] : (T)0;
-  d = wave_allsum(d);
+  d = mgp_wave_sum(d);
   if (lane == 0) red[wave] = d;
   T s = 0;
 #pragma unroll
@@ -603,7 +389,7 @@ __global__ __launch_bounds__(NT) void d1m_update_kernel(MgpCgCtrl* __restrict__ 
     v[off + i] = vn;
     r[off + i] = rn;
   }
-  const T prz = wave_allsum(ok ? zn * rn : (T)0), prr = wave_allsum(ok ? rn * rn : (T)0);
+  const T prz = mgp_wave_sum(ok ? zn * rn : (T)0), prr = mgp_wave_sum(ok ? rn * rn : (T)0);
   if (lane == 0) {
     T* cp = cpart + (long)col * 2 * CP;
     cp[c] = prz;
@@ -615,6 +401,8 @@ __global__ __launch_bounds__(NT) void d1m_update_kernel(MgpCgCtrl* __restrict__ 
 // workgroup barrier that orders LDS only (no wait for vector-memory operations in flight)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// write-through store / L1-bypassing load of one element (global_store/load ... sc1): the two halves of a hand-off
+// between resident workgroups without fences (MI355X_MICROARCH.md, hand-off table)
 template <typename T>
 __device__ __forceinline__ T ld_sc1(const T* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1480,8 +1268,8 @@ __global__ __launch_bounds__(1024) void d1_persist_full_kernel(MgpCgCtrl* __rest
 }
 
 template <typename T>
-int d1_layout(MgpDense1* st, void* arena, long n) {
-  // arena (bt = columns): tpart[bt][ntiles] | cpart[bt][2 CP] | scal[bt][2] | pb[2][bt][n] | zpub[n] |
+void d1_layout(MgpDense1* st, void* arena, long n) {
+  // arena (bt = columns): tpart[bt][ntiles] | cpart[bt][2 CP] | scal[bt][2] | pb[2][bt][n] | zpub[bt][n] |
   //        (bt > 1) the slots Q[bt][nt][n] | hand-off words (a 128-byte line of their own: error word, two stop words)
   //        | granules of the register-resident form: Qg[nt n] | wpg[256] | cg[128] | zg[n]  (x W 8-byte words each)
   const long nt = (n + 63) / 64, ntiles = nt * (nt + 1) / 2, bt = st->bt;
@@ -1497,14 +1285,12 @@ int d1_layout(MgpDense1* st, void* arena, long n) {
   a += 2 * bt * n;
   st->zpub = a;
   a += bt * n;
-  st->Qm = nullptr;
-  if (bt > 1) {
-    st->Qm = a;
+  if (bt > 1) {  // one column keeps dense.hip's slots Q[nt][n], which mgp_dense1_begin has put into st->Q
+    st->Q = a;
     a += bt * nt * n;
   }
   st->sync = (void*)(((uintptr_t)a + 127) & ~(uintptr_t)127);
   st->gran = (char*)st->sync + 128;
-  return MGP_OK;
 }
 
 // granule elements: Qg (round-robin triangle form: nt n; full form: bt nt 8 64; super-block form: bt nt (S + 1) 64 with
@@ -1583,36 +1369,44 @@ int mgp_dense1_begin(mgp_handle* h, MgpDense1* st, int dtype, const void* A, int
   st->nt = (int)((n + 63) / 64);
   st->ntiles = (long)st->nt * (st->nt + 1) / 2;
   st->persist = persist;
+  // the product's slots and the tile table (dense.hip owns both); several columns take slots in the arena instead
+  MGP_TRY(mgp_symm_gemv_tri_prepare(h, dtype, n, &st->Q, &st->tab));
   if (dtype == MGP_F64) d1_layout<double>(st, arena, n);
   else d1_layout<float>(st, arena, n);
   MGP_HIP(h, hipMemsetAsync(st->cpart, 0, (size_t)bt * 2 * CP * mgp_elem(dtype), h->stream));  // shares of chunks beyond nt stay 0
-  // the hand-off error word and -- a tag left by an earlier solve must never match an epoch of this one -- every granule
+  // the hand-off error word, the two stop words and -- a tag left by an earlier solve must never match an epoch of this
+  // one -- every granule
   MGP_HIP(h, hipMemsetAsync(st->sync, 0, 128 + (persist ? d1_gran_bytes(dtype, n, bt) : 0), h->stream));
-  // the product's slots and the tile table (dense.hip owns both)
-  MGP_TRY(mgp_symm_gemv_tri_prepare(h, dtype, n, &st->Q, &st->tab));
-  if (bt > 1) {
-    const dim3 g((unsigned)st->nt, (unsigned)bt);
-    if (dtype == MGP_F64)
-      hipLaunchKernelGGL((d1m_init_kernel<double>), g, dim3(64), 0, h->stream, ctrl, (const double*)B, (const double*)av,
-                         (double*)r, (const double*)dinv, (double*)st->cpart, (double*)st->scal, (double*)st->zpub,
-                         (long)n, (int*)st->sync + 1);
-    else
-      hipLaunchKernelGGL((d1m_init_kernel<float>), g, dim3(64), 0, h->stream, ctrl, (const float*)B, (const float*)av,
-                         (float*)r, (const float*)dinv, (float*)st->cpart, (float*)st->scal, (float*)st->zpub, (long)n,
-                         (int*)st->sync + 1);
-    MGP_LAUNCH_CHECK(h);
+  const dim3 g((unsigned)st->nt, (unsigned)bt);
+  mgp_with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((d1_init_kernel<T>), g, dim3(64), 0, h->stream, ctrl, (const T*)B, (const T*)av, (T*)r,
+                       (const T*)dinv, (T*)st->cpart, (T*)st->scal, (T*)st->zpub, (long)n);
     return MGP_OK;
-  }
-  if (dtype == MGP_F64)
-    hipLaunchKernelGGL((d1_init_kernel<double>), dim3((unsigned)st->nt), dim3(64), 0, h->stream, ctrl, (const double*)B,
-                       (const double*)av, (double*)r, (const double*)dinv, (double*)st->cpart, (double*)st->scal,
-                       (double*)st->zpub, (long)n);
-  else
-    hipLaunchKernelGGL((d1_init_kernel<float>), dim3((unsigned)st->nt), dim3(64), 0, h->stream, ctrl, (const float*)B,
-                       (const float*)av, (float*)r, (const float*)dinv, (float*)st->cpart, (float*)st->scal,
-                       (float*)st->zpub, (long)n);
+  });
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
+}
+
+// Element type, Jacobi flag and column count of a solve as compile-time constants of a generic lambda (the idiom of
+// mgp_with_kind / mgp_with_dp): f(T{}, bool_constant<JAC>, integral_constant<int, BT>), BT = 1 .. 8
+template <typename F>
+static int d1_with_form(const MgpDense1* st, F&& f) {
+  return mgp_with_dtype(st->dtype, [&](auto t) {
+    const auto with_bt = [&](auto jac) {
+      switch (st->bt) {
+        case 1: return f(t, jac, std::integral_constant<int, 1>{});
+        case 2: return f(t, jac, std::integral_constant<int, 2>{});
+        case 3: return f(t, jac, std::integral_constant<int, 3>{});
+        case 4: return f(t, jac, std::integral_constant<int, 4>{});
+        case 5: return f(t, jac, std::integral_constant<int, 5>{});
+        case 6: return f(t, jac, std::integral_constant<int, 6>{});
+        case 7: return f(t, jac, std::integral_constant<int, 7>{});
+        default: return f(t, jac, std::integral_constant<int, 8>{});
+      }
+    };
+    return st->dinv ? with_bt(std::true_type{}) : with_bt(std::false_type{});
+  });
 }
 
 template <typename T>
@@ -1633,12 +1427,12 @@ static D1PBuf d1_pbuf(const MgpDense1* st) {
 int mgp_dense1_persist_run(mgp_handle* h, const MgpDense1* st) {
   const dim3 grid((unsigned)d1_persist_grid(h));
   const dim3 sgrid((unsigned)st->nt, (unsigned)st->bt);
-  if (st->dtype == MGP_F64)
-    hipLaunchKernelGGL((d1_persist_seed_kernel<double>), sgrid, dim3(64), 0, h->stream, (const double*)st->zpub,
-                       (const double*)st->cpart, d1_pbuf<double>(st), (long)st->n, st->nt);
-  else
-    hipLaunchKernelGGL((d1_persist_seed_kernel<float>), sgrid, dim3(64), 0, h->stream, (const float*)st->zpub,
-                       (const float*)st->cpart, d1_pbuf<float>(st), (long)st->n, st->nt);
+  mgp_with_dtype(st->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((d1_persist_seed_kernel<T>), sgrid, dim3(64), 0, h->stream, (const T*)st->zpub,
+                       (const T*)st->cpart, d1_pbuf<T>(st), (long)st->n, st->nt);
+    return MGP_OK;
+  });
   MGP_LAUNCH_CHECK(h);
   unsigned long long* trace = nullptr;
   const char* trace_path = getenv("MGP_D1_TRACE");
@@ -1652,73 +1446,31 @@ int mgp_dense1_persist_run(mgp_handle* h, const MgpDense1* st) {
   const int form = d1_persist_form(h, (long)st->n, st->bt);
   const bool full = form == 1 && d1_full_geometry(h, st->nt, &Rg, &rpg);
   const bool blk = form == 2 && d1_blk_geometry(h, st->nt, &Sb);
-  if (form == 0 || (st->bt > 1 && !full && !blk))
+  if (!full && !blk)
     return mgp_fail(h, MGP_E_BADARG, "dense CG: no register-resident form for n = %ld with %d columns", (long)st->n, st->bt);
-#define MGP_D1B(TT, JV, BTV)                                                                                         \
-  do {                                                                                                               \
-    const size_t dyn = D1Blk<TT, BTV>::kDyn;                                                                         \
-    MGP_HIP(h, hipFuncSetAttribute((const void*)d1_persist_blk_kernel<TT, JV, BTV>,                                  \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));                           \
-    hipLaunchKernelGGL((d1_persist_blk_kernel<TT, JV, BTV>), grid, dim3(768), dyn, h->stream, st->ctrl,                \
-                       d1_pbuf<TT>(st), (const TT*)st->A, (long)st->n, st->nt, Sb, (TT*)st->r, (TT*)st->V,            \
-                       (const TT*)st->dinv, (TT*)st->cpart, (TT)st->thr, (TT)st->min_float, st->max_it,               \
-                       h->d1_first_poll_sleep, h->d1_inject_absent, h->d1_owner_spread, trace);                                                               \
-  } while (0)
-#define MGP_D1BB(TT, JV)                     \
-  switch (st->bt) {                          \
-    case 1: MGP_D1B(TT, JV, 1); break;       \
-    case 2: MGP_D1B(TT, JV, 2); break;       \
-    case 3: MGP_D1B(TT, JV, 3); break;       \
-    case 4: MGP_D1B(TT, JV, 4); break;       \
-    case 5: MGP_D1B(TT, JV, 5); break;       \
-    case 6: MGP_D1B(TT, JV, 6); break;       \
-    case 7: MGP_D1B(TT, JV, 7); break;       \
-    default: MGP_D1B(TT, JV, 8); break;      \
-  }
-#define MGP_D1F(TT, JV, BTV)                                                                                         \
-  do {                                                                                                               \
-    const size_t dyn = (size_t)BTV * 16 * 64 * sizeof(TT);                                                           \
-    MGP_HIP(h, hipFuncSetAttribute((const void*)d1_persist_full_kernel<TT, JV, BTV>,                                 \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));                           \
-    hipLaunchKernelGGL((d1_persist_full_kernel<TT, JV, BTV>), grid, dim3(1024), dyn, h->stream, st->ctrl,              \
-                       d1_pbuf<TT>(st), (const TT*)st->A, (long)st->n, st->nt, Rg, rpg, (TT*)st->r, (TT*)st->V,       \
-                       (const TT*)st->dinv, (TT*)st->cpart, (TT)st->thr, (TT)st->min_float, st->max_it,               \
-                       h->d1_first_poll_sleep, h->d1_inject_absent, h->d1_owner_spread, trace);                                                               \
-  } while (0)
-#define MGP_D1FB(TT, JV)                     \
-  switch (st->bt) {                          \
-    case 1: MGP_D1F(TT, JV, 1); break;       \
-    case 2: MGP_D1F(TT, JV, 2); break;       \
-    case 3: MGP_D1F(TT, JV, 3); break;       \
-    case 4: MGP_D1F(TT, JV, 4); break;       \
-    case 5: MGP_D1F(TT, JV, 5); break;       \
-    case 6: MGP_D1F(TT, JV, 6); break;       \
-    case 7: MGP_D1F(TT, JV, 7); break;       \
-    default: MGP_D1F(TT, JV, 8); break;      \
-  }
-#define MGP_D1P(TT, JV)                                                                                             \
-  do {                                                                                                              \
-    if (full) {                                                                                                     \
-      MGP_D1FB(TT, JV);                                                                                             \
-      break;                                                                                                        \
-    }                                                                                                               \
-    if (blk) {                                                                                                      \
-      MGP_D1BB(TT, JV);                                                                                             \
-      break;                                                                                                        \
-    }                                                                                                               \
-  } while (0)
-  if (st->dtype == MGP_F64) {
-    if (st->dinv) MGP_D1P(double, true);
-    else MGP_D1P(double, false);
-  } else {
-    if (st->dinv) MGP_D1P(float, true);
-    else MGP_D1P(float, false);
-  }
-#undef MGP_D1F
-#undef MGP_D1FB
-#undef MGP_D1B
-#undef MGP_D1BB
-#undef MGP_D1P
+  MGP_TRY(d1_with_form(st, [&](auto t, auto jac, auto btc) -> int {
+    using T = decltype(t);
+    constexpr bool JAC = decltype(jac)::value;
+    constexpr int BT = decltype(btc)::value;
+    if (full) {
+      const size_t dyn = (size_t)BT * 16 * 64 * sizeof(T);
+      MGP_HIP(h, hipFuncSetAttribute((const void*)d1_persist_full_kernel<T, JAC, BT>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+      hipLaunchKernelGGL((d1_persist_full_kernel<T, JAC, BT>), grid, dim3(1024), dyn, h->stream, st->ctrl,
+                         d1_pbuf<T>(st), (const T*)st->A, (long)st->n, st->nt, Rg, rpg, (T*)st->r, (T*)st->V,
+                         (const T*)st->dinv, (T*)st->cpart, (T)st->thr, (T)st->min_float, st->max_it,
+                         h->d1_first_poll_sleep, h->d1_inject_absent, h->d1_owner_spread, trace);
+    } else {
+      const size_t dyn = D1Blk<T, BT>::kDyn;
+      MGP_HIP(h, hipFuncSetAttribute((const void*)d1_persist_blk_kernel<T, JAC, BT>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+      hipLaunchKernelGGL((d1_persist_blk_kernel<T, JAC, BT>), grid, dim3(768), dyn, h->stream, st->ctrl,
+                         d1_pbuf<T>(st), (const T*)st->A, (long)st->n, st->nt, Sb, (T*)st->r, (T*)st->V,
+                         (const T*)st->dinv, (T*)st->cpart, (T)st->thr, (T)st->min_float, st->max_it,
+                         h->d1_first_poll_sleep, h->d1_inject_absent, h->d1_owner_spread, trace);
+    }
+    return MGP_OK;
+  }));
   MGP_LAUNCH_CHECK(h);
   if (trace) {  // diagnosis only: drains the stream
     std::vector<unsigned long long> host(kTraceWords);
@@ -1742,100 +1494,44 @@ int mgp_dense1_persist_run(mgp_handle* h, const MgpDense1* st) {
   return MGP_OK;
 }
 
-template <typename T, bool JAC>
-static int d1_step_t(mgp_handle* h, const MgpDense1* st, long k) {
-  const int kk = (int)(k & 1);
-  const T* p_old = (const T*)st->pb[(k + 1) & 1];
-  T* p_new = (T*)st->pb[k & 1];
-  hipLaunchKernelGGL((d1_tile_kernel<T, JAC>), dim3((unsigned)st->ntiles), dim3(256), 0, h->stream, st->ctrl,
-                     (const T*)st->A, (long)st->n, (const T*)st->r, (const T*)st->dinv, p_old, p_new,
-                     (const T*)st->cpart, (T*)st->scal, kk, (const int2*)st->tab, (T*)st->Q, (T*)st->tpart, (T)st->thr,
-                     (T)st->min_float, st->max_it, (int*)st->sync + 1);
-  MGP_LAUNCH_CHECK(h);
-#define MGP_D1U(NTV, PERV, TPMV)                                                                                     \
-  hipLaunchKernelGGL((d1_update_kernel<T, JAC, NTV, PERV, TPMV>), dim3((unsigned)st->nt), dim3(NTV), 0, h->stream,     \
-                     st->ctrl, (const T*)st->Q, st->nt, (const T*)st->tpart, st->ntiles, (const T*)st->scal, kk,      \
-                     (const T*)p_new, (T*)st->V, (T*)st->r, (const T*)st->dinv, (T*)st->cpart, (long)st->n,           \
-                     (T)st->min_float, (const int*)st->sync + 1)
-  if (st->nt <= 32) MGP_D1U(256, 8, 3);         // 528 tiles
-  else if (st->nt <= 64) MGP_D1U(256, 16, 9);   // 2080 tiles
-  else MGP_D1U(512, 16, 17);                    // nt <= 128: 8256 tiles
-#undef MGP_D1U
-  MGP_LAUNCH_CHECK(h);
-  return MGP_OK;
-}
-
+// T_k, U_k for BT columns; the update's (threads, slots per wave, tile shares per thread) by the number of chunks
 template <typename T, bool JAC, int BT>
-static int d1m_step_t(mgp_handle* h, const MgpDense1* st, long k) {
+static int d1_step(mgp_handle* h, const MgpDense1* st, long k) {
   const int kk = (int)(k & 1);
   const T* p_old = (const T*)st->pb[(k + 1) & 1];
   T* p_new = (T*)st->pb[k & 1];
   int* stopw = (int*)st->sync + 1;
-  hipLaunchKernelGGL((d1m_tile_kernel<T, JAC, BT>), dim3((unsigned)st->ntiles), dim3(256), 0, h->stream, st->ctrl,
+  hipLaunchKernelGGL((d1_tile_kernel<T, JAC, BT>), dim3((unsigned)st->ntiles), dim3(256), 0, h->stream, st->ctrl,
                      (const T*)st->A, (long)st->n, (const T*)st->r, (const T*)st->dinv, p_old, p_new,
-                     (const T*)st->cpart, (T*)st->scal, kk, (const int2*)st->tab, (T*)st->Qm, st->nt, (T*)st->tpart,
+                     (const T*)st->cpart, (T*)st->scal, kk, (const int2*)st->tab, (T*)st->Q, st->nt, (T*)st->tpart,
                      st->ntiles, (T)st->thr, (T)st->min_float, st->max_it, stopw);
   MGP_LAUNCH_CHECK(h);
-  const dim3 g((unsigned)st->nt, (unsigned)BT);
-#define MGP_D1MU(NTV, PERV, TPMV)                                                                                    \
-  hipLaunchKernelGGL((d1m_update_kernel<T, JAC, NTV, PERV, TPMV>), g, dim3(NTV), 0, h->stream, st->ctrl,               \
-                     (const T*)st->Qm, st->nt, (const T*)st->tpart, st->ntiles, (const T*)st->scal, kk,               \
-                     (const T*)p_new, (T*)st->V, (T*)st->r, (const T*)st->dinv, (T*)st->cpart, (long)st->n,           \
-                     (T)st->min_float, (const int*)stopw)
-  if (st->nt <= 32) MGP_D1MU(256, 8, 3);
-  else if (st->nt <= 64) MGP_D1MU(256, 16, 9);
-  else MGP_D1MU(512, 16, 17);
-#undef MGP_D1MU
+  const auto update = st->nt <= 32   ? d1_update_kernel<T, JAC, 256, 8, 3>     // 528 tiles
+                      : st->nt <= 64 ? d1_update_kernel<T, JAC, 256, 16, 9>    // 2080 tiles
+                                     : d1_update_kernel<T, JAC, 512, 16, 17>;  // nt <= 128: 8256 tiles
+  hipLaunchKernelGGL(update, dim3((unsigned)st->nt, (unsigned)BT), dim3(st->nt <= 64 ? 256 : 512), 0, h->stream,
+                     st->ctrl, (const T*)st->Q, st->nt, (const T*)st->tpart, st->ntiles, (const T*)st->scal, kk,
+                     (const T*)p_new, (T*)st->V, (T*)st->r, (const T*)st->dinv, (T*)st->cpart, (long)st->n,
+                     (T)st->min_float, (const int*)stopw);
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
-}
-
-template <typename T, bool JAC>
-static int d1m_step_bt(mgp_handle* h, const MgpDense1* st, long k) {
-  switch (st->bt) {
-    case 2: return d1m_step_t<T, JAC, 2>(h, st, k);
-    case 3: return d1m_step_t<T, JAC, 3>(h, st, k);
-    case 4: return d1m_step_t<T, JAC, 4>(h, st, k);
-    case 5: return d1m_step_t<T, JAC, 5>(h, st, k);
-    case 6: return d1m_step_t<T, JAC, 6>(h, st, k);
-    case 7: return d1m_step_t<T, JAC, 7>(h, st, k);
-    default: return d1m_step_t<T, JAC, 8>(h, st, k);
-  }
 }
 
 // enqueue iteration k (k = 1, 2, ...): T_k, U_k
 int mgp_dense1_step(mgp_handle* h, const MgpDense1* st, int64_t k) {
-  if (st->bt > 1) {
-    if (st->dtype == MGP_F64)
-      return st->dinv ? d1m_step_bt<double, true>(h, st, k) : d1m_step_bt<double, false>(h, st, k);
-    return st->dinv ? d1m_step_bt<float, true>(h, st, k) : d1m_step_bt<float, false>(h, st, k);
-  }
-  if (st->dtype == MGP_F64)
-    return st->dinv ? d1_step_t<double, true>(h, st, k) : d1_step_t<double, false>(h, st, k);
-  return st->dinv ? d1_step_t<float, true>(h, st, k) : d1_step_t<float, false>(h, st, k);
+  return d1_with_form(st, [&](auto t, auto jac, auto btc) {
+    return d1_step<decltype(t), decltype(jac)::value, decltype(btc)::value>(h, st, k);
+  });
 }
 
 // statistics (rz, err, over) and the gate word for the host poll
 int mgp_dense1_finish(mgp_handle* h, MgpDense1* st, void* rz, void* err, int* over) {
-  if (st->bt > 1) {
-    if (st->dtype == MGP_F64)
-      hipLaunchKernelGGL((d1m_finish_kernel<double>), dim3(1), dim3(512), 0, h->stream, st->ctrl, (const int*)st->sync,
-                         (const double*)st->cpart, (double*)rz, (double*)err, over, (double)st->thr, st->max_it, st->bt);
-    else
-      hipLaunchKernelGGL((d1m_finish_kernel<float>), dim3(1), dim3(512), 0, h->stream, st->ctrl, (const int*)st->sync,
-                         (const float*)st->cpart, (float*)rz, (float*)err, over, (float)st->thr, st->max_it, st->bt);
-    MGP_LAUNCH_CHECK(h);
+  mgp_with_dtype(st->dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((d1_finish_kernel<T>), dim3(1), dim3(512), 0, h->stream, st->ctrl, (const int*)st->sync,
+                       (const T*)st->cpart, (T*)rz, (T*)err, over, (T)st->thr, st->max_it, st->bt);
     return MGP_OK;
-  }
-  if (st->dtype == MGP_F64)
-    hipLaunchKernelGGL((d1_finish_kernel<double>), dim3(1), dim3(64), 0, h->stream, st->ctrl,
-                       (const int*)st->sync, (const double*)st->cpart, (double*)rz, (double*)err,
-                       over, (double)st->thr, st->max_it);
-  else
-    hipLaunchKernelGGL((d1_finish_kernel<float>), dim3(1), dim3(64), 0, h->stream, st->ctrl,
-                       (const int*)st->sync, (const float*)st->cpart, (float*)rz, (float*)err,
-                       over, (float)st->thr, st->max_it);
+  });
   MGP_LAUNCH_CHECK(h);
   return MGP_OK;
 }
-

@@ -325,11 +325,11 @@ struct MgpDense1 {
   long ntiles = 0;
   const void* A = nullptr;
   const void* dinv = nullptr;
+  // Q: the product's slots [bt][nt][n] -- dense.hip's for one right-hand side, a block of the arena for several
   void *V = nullptr, *r = nullptr, *Q = nullptr, *tpart = nullptr, *cpart = nullptr, *scal = nullptr;
   void* pb[2] = {nullptr, nullptr};
   // register-resident form (cg_dense1.hip, round 4): published z, the workgroups' shares of p.Ap, the hand-off flags
-  int persist = 0, bt = 1;  // bt: right-hand sides (2..8: the multi-column kernels, their slots in Qm)
-  void* Qm = nullptr;
+  int persist = 0, bt = 1;  // bt: right-hand sides, 1 .. 8
   void *zpub = nullptr, *sync = nullptr, *gran = nullptr;
   const void* tab = nullptr;
   MgpCgCtrl* ctrl = nullptr;

@@ -7,7 +7,11 @@ Against `oracle/cg.py` (line-for-line restatement of `conjugate_gradient.py:44-1
 after exactly k steps, step counts and stopping quantity of converged solves, the iteration cap, the guard floor,
 Jacobi preconditioning, an initial solution, ragged n (n % 64 != 0), fp32, and -- the path change must not be
 visible -- agreement with the several-right-hand-side path (a different set of kernels) on the same system.
+One kernel family carries 1 .. 8 columns on the two-launch form: a column's iterate is the same bits alone and in
+company (test_a_column_does_not_depend_on_its_company).
 """
+
+import functools
 
 import numpy as np
 import pytest
@@ -199,7 +203,7 @@ def test_one_column_agrees_with_the_several_column_path():
 @pytest.mark.parametrize("Bt", [2, 5, 8])
 def test_several_columns_on_the_tile_scheme(n, Bt):
     """2 .. 8 right-hand sides (the reference's default num_probes = 5, cggp/models.py:286): the two-launch tile scheme
-    with BT columns (csrc/cg_dense1.hip, d1m_*) where it is the faster route (Bt <= 4 at n <= 4096, <= 6 above; every
+    with BT columns (csrc/cg_dense1.hip, d1_tile_kernel<BT> + d1_update_kernel) where it is the faster route (Bt <= 4 at n <= 4096, <= 6 above; every
     BT up to 8 is forced through it in test_every_form_...), the skinny product + fused update otherwise -- either
     way: k steps against the oracle, column by column; the `any`
     stopping rule (:59-62) -- all columns iterate until the slowest one is under the threshold; run-to-run identity;
@@ -234,6 +238,69 @@ def test_several_columns_on_the_tile_scheme(n, Bt):
                                           max_steps_cycle=4)
         o_sj, _ = ocg.conjugate_gradient(A, rhs, v0, 0.0, ocg.JacobiPreconditioner(), max_iterations=3, max_steps_cycle=4)
         assert relerr(sj, o_sj) < 1e-9
+
+
+@functools.lru_cache(maxsize=1)  # the cases come grouped by system; the oracle runs once per (system, Jacobi)
+def company_system(n, dtype, cols):
+    """fp64: `problem` with a diagonal worth scaling by (test_jacobi_preconditioner); fp32: the system of test_fp32,
+    rounded to float32.  `cols` right-hand sides; with the k = 5 oracle iterates, Jacobi off and on."""
+    A, _ = problem(n, seed=n, noise=0.1 if dtype == "f64" else 1.0)
+    if dtype == "f64":
+        A = A * np.outer(np.linspace(1, 3, n), np.linspace(1, 3, n))
+    rhs = np.random.default_rng(n + cols).standard_normal((cols, n))
+    if dtype == "f32":
+        A, rhs = A.astype(np.float32).astype(np.float64), rhs.astype(np.float32).astype(np.float64)
+    oracle = {}
+    for jac in (False, True):
+        pre = ocg.JacobiPreconditioner() if jac else None
+        o_sol, (o_steps, o_err) = ocg.conjugate_gradient(A, rhs, np.zeros((cols, n)), 0.0, pre, max_iterations=5,
+                                                         max_steps_cycle=6)
+        assert o_steps == 5
+        oracle[jac] = (o_sol, o_err)
+    tdt = torch.float64 if dtype == "f64" else torch.float32
+    return T(A, tdt), T(rhs, tdt), oracle
+
+
+# n: the smallest sizes, all with a ragged last tile, that reach each instantiation of the update kernel --
+# nt = 17 <256, 8, 3>, nt = 34 <256, 16, 9>, nt = 66 <512, 16, 17>
+@pytest.mark.parametrize("n,dtype,cols,jac", [(1025, "f64", 3, False), (1025, "f64", 3, True), (1025, "f64", 8, False),
+                                              (1025, "f32", 3, False), (2113, "f64", 3, False),
+                                              (2113, "f64", 3, True), (4161, "f64", 3, False),
+                                              (4161, "f64", 3, True)])
+def test_a_column_does_not_depend_on_its_company(n, dtype, cols, jac, monkeypatch):
+    """Two launches per iteration (MGP_CG_DENSE1=1; MGP_CG_DENSE1_COLS=8 so that eight columns at n = 1025 take them
+    too, csrc/cg.hip `d1_cols`): the k = 5 iterate and error statistic of a column are the same bits whether it is
+    solved alone or with the others -- one kernel family, column = blockIdx.y, the same additions in the same order.
+    The joint solve against oracle/cg.py at the bars of test_fixed_steps_match_oracle (fp32: of test_fp32); every
+    call twice with the same bits."""
+    import switch_forms
+    from cggp.conjugate_gradient import JacobiPreconditioner, conjugate_gradient
+    k = 5
+    A, rhs, oracle = company_system(n, dtype, cols)
+    o_sol, o_err = oracle[jac]
+
+    def solve(b):
+        runs = []
+        for _ in range(2):
+            sol, (steps, err) = conjugate_gradient(A, b, None, 0.0, JacobiPreconditioner() if jac else None,
+                                                   max_iterations=k, max_steps_cycle=k + 1)
+            assert int(steps) == k
+            runs.append((sol.clone(), err.clone()))
+        assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
+        return runs[0]
+
+    with switch_forms.switched(monkeypatch, {"MGP_CG_DENSE1": "1", "MGP_CG_DENSE1_COLS": "8"}):
+        V, err = solve(rhs)
+        assert V.shape == (cols, n) and err.shape == (cols, 1)
+        bar_v, bar_e = (1e-9, 1e-6) if dtype == "f64" else (5e-4, 5e-3)
+        for c in range(cols):
+            d_v = relerr(V[c], o_sol[c])
+            d_e = abs(float(err[c]) - float(o_err[c, 0])) / float(o_err[c, 0])
+            print(f"n={n} {dtype} jac={jac} column {c} of {cols}: iterate {d_v:.2e} (bar {bar_v:g}) err {d_e:.2e} (bar {bar_e:g})")
+            assert d_v < bar_v and d_e < bar_e, (c, d_v, d_e)
+        for c in range(cols):
+            v1, e1 = solve(rhs[c:c + 1].contiguous())
+            assert torch.equal(v1[0], V[c]) and torch.equal(e1[0], err[c]), c
 
 
 @pytest.mark.parametrize("n,Bt", [(2049, 1), (2500, 4), (3000, 6), (3520, 2), (4001, 3), (4095, 5), (4096, 6), (4001, 7), (3000, 8)])

@@ -1,5 +1,5 @@
-"""In-run A/B of the dense CG with 2..8 right-hand sides: the tile scheme with BT columns (csrc/cg_dense1.hip, d1m_*,
-default) against round 3's route -- skinny MFMA product + fused update (MGP_CG_DENSE1_COLS=1).  One child process per
+"""In-run A/B of the dense CG with 2..8 right-hand sides: the tile scheme with BT columns (csrc/cg_dense1.hip,
+d1_tile_kernel<BT> + d1_update_kernel, default) against round 3's route -- skinny MFMA product + fused update (MGP_CG_DENSE1_COLS=1).  One child process per
 variant (switches are read at handle creation), two alternations.  usage: python tools/ab_dense_cols.py"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
