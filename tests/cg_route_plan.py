@@ -12,6 +12,10 @@ tests/test_cg_route_plan.py checks on the CPU that CASES reaches every tier on b
 and a reduced product in each thread-count family, both block sizes and all six modes of the generic update kernel;
 tests/test_gpu_cg_routes.py runs the cases against oracle/cg.py.  Every case has more right-hand sides than the
 tile scheme of csrc/cg_dense1.hip takes (8), a preconditioner it does not take, or is a recording solve.
+
+The cases stop before any breakdown guard fires.  tests/guard_plan.py holds the systems and cases on which they do fire
+(columns frozen from step 0, frozen after converging beside live ones, either guard alone, other floors) for the same
+kernel sites and for the forms of csrc/cg_dense1.hip.
 """
 
 from collections import namedtuple

@@ -5,7 +5,11 @@ tests/test_gpu_parity.py::test_cg_fixed_iterations_match_oracle (1e-9 relative o
 0.5 rz), each solve twice with the same bits.
 
 fp32 has no fixed-step bar elsewhere: a case's bar is four times the distance of the oracle on float32 copies from its
-own float64 run on that case (cg_route_plan.py)."""
+own float64 run on that case (cg_route_plan.py).
+
+No breakdown guard fires on these cases (every column is live at every step, asserted below).  The guards, columns of
+different lifetimes in one batch and the stopping rule are held to the oracle on every one of these kernel sites by
+tests/test_gpu_cg_guards.py, on the cases of tests/guard_plan.py."""
 
 import functools
 
