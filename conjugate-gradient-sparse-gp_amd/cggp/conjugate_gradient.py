@@ -657,6 +657,32 @@ def _solve_device(op, rhs, initial_solution, error_threshold, preconditioner, ma
     return sol, stats, err
 
 
+def _adjoint_solve(op, sol, rhs, err, dx, cfg, zero_start):
+    """db with db A = dx for the backward pass of a solve `sol A = rhs` (rows; `err` = 0.5 rz of that solve): the
+    shortcut or the warm start of `_CGFunction` where they apply, else the device CG from zero."""
+    dx = dx.contiguous()
+    db = None
+    warm = None
+    if zero_start:
+        rr = (rhs * rhs).sum(dim=1, keepdim=True)
+        c = (dx * rhs).sum(dim=1, keepdim=True) / torch.where(rr > 0, rr, torch.ones_like(rr))
+        tol = 1e-12 if dx.dtype == torch.float64 else 1e-5
+        if bool(((dx - c * rhs).abs().max() <= tol * dx.abs().max()).item()):
+            # err = 0.5 rz of the forward solve (= 0.5||r||^2 for the identity preconditioner; for
+            # others recompute the true residual of c*sol below through the warm start)
+            thr = float(cfg[0])
+            plain = cfg[1] is None or isinstance(cfg[1], EyePreconditioner)
+            if plain and bool(((c * c) * err <= thr).all().item()):
+                db = c * sol
+                conjugate_gradient.backward_shortcuts += 1
+            else:
+                warm = (c * sol).contiguous()
+                conjugate_gradient.backward_warm_starts += 1
+    if db is None:
+        db, _, _ = _solve_device(op, dx, warm, *cfg)
+    return db
+
+
 class _CGFunction(torch.autograd.Function):
     """Custom gradient of reference :100-118: db = CG(A, dx) from zero, dA = -solution^T @ db.
 
@@ -685,27 +711,7 @@ class _CGFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx, _derr):
         sol, rhs, err = ctx.saved_tensors
-        op = as_operator(ctx.matrix)
-        dx = dx.contiguous()
-        db = None
-        warm = None
-        if ctx.zero_start:
-            rr = (rhs * rhs).sum(dim=1, keepdim=True)
-            c = (dx * rhs).sum(dim=1, keepdim=True) / torch.where(rr > 0, rr, torch.ones_like(rr))
-            tol = 1e-12 if dx.dtype == torch.float64 else 1e-5
-            if bool(((dx - c * rhs).abs().max() <= tol * dx.abs().max()).item()):
-                # err = 0.5 rz of the forward solve (= 0.5||r||^2 for the identity preconditioner; for
-                # others recompute the true residual of c*sol below through the warm start)
-                thr = float(ctx.cfg[0])
-                plain = ctx.cfg[1] is None or isinstance(ctx.cfg[1], EyePreconditioner)
-                if plain and bool(((c * c) * err <= thr).all().item()):
-                    db = c * sol
-                    conjugate_gradient.backward_shortcuts += 1
-                else:
-                    warm = (c * sol).contiguous()
-                    conjugate_gradient.backward_warm_starts += 1
-        if db is None:
-            db, _, _ = _solve_device(op, dx, warm, *ctx.cfg)
+        db = _adjoint_solve(as_operator(ctx.matrix), sol, rhs, err, dx, ctx.cfg, ctx.zero_start)
         dA = None
         if isinstance(ctx.matrix, torch.Tensor) and ctx.needs_input_grad[0]:
             dA = -(sol.t() @ db)  # [n,Bt]x[Bt,n] library GEMM (rank-Bt update)
@@ -753,17 +759,21 @@ class ConjugateGradient:
         self.check_every = check_every
         self.last_stats = None
 
+    def config(self, n):
+        """The argument tuple of the device solve for an n x n system, defaults resolved as the reference does."""
+        max_iterations = self.max_iterations if self.max_iterations is not None else n  # :190-192
+        max_steps_cycle = self.max_steps_cycle if self.max_steps_cycle is not None else max_iterations + 1  # :194-196
+        return (self.error_threshold, self.preconditioner, max_iterations, max_steps_cycle, self.min_float,
+                self.check_every)
+
     def solve_with_stats(self, matrix, rhs, initial_solution=None):
         """`stats_conjugate_gradient` of `cggp/paper_condition_wasserstein.py:262-294`."""
         rhs_t = rhs.t().contiguous()  # :183
         init_t = None if initial_solution is None else initial_solution.t().contiguous()  # :185-188
-        n = matrix.shape[-1]
-        max_iterations = self.max_iterations if self.max_iterations is not None else n  # :190-192
-        max_steps_cycle = self.max_steps_cycle if self.max_steps_cycle is not None else max_iterations + 1  # :194-196
+        thr, pre, max_iterations, max_steps_cycle, min_float, check_every = self.config(matrix.shape[-1])
         sol, stats = conjugate_gradient(
-            matrix, rhs_t, init_t, self.error_threshold, preconditioner=self.preconditioner,
-            max_iterations=max_iterations, max_steps_cycle=max_steps_cycle, min_float=self.min_float,
-            check_every=self.check_every)
+            matrix, rhs_t, init_t, thr, preconditioner=pre, max_iterations=max_iterations,
+            max_steps_cycle=max_steps_cycle, min_float=min_float, check_every=check_every)
         self.last_stats = stats
         return sol.t().contiguous(), stats  # :211
 

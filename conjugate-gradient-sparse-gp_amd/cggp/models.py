@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .conjugate_gradient import (ConjugateGradient, KxxNoiseOperator, PivotedCholeskyPreconditioner, SgprNormalOperator,
-                                 SubsampledNormalPreconditioner)
+from .conjugate_gradient import (ConjugateGradient, KmmLambdaOperator, KxxNoiseOperator, PivotedCholeskyPreconditioner,
+                                 SgprNormalOperator, SubsampledNormalPreconditioner)
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
 from .slq import slq_log_quadratic
@@ -246,29 +246,52 @@ class ClusterGP:
 
 
 class CGGP(ClusterGP):
-    """`cggp/models.py:279-354`."""
+    """`cggp/models.py:279-354`.
 
-    def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, **kwargs):
+    `matrix_free=True`: nothing [M, M] is allocated by any method.  Every solve takes the operator
+    `KmmLambdaOperator(kernel, Z, diag_variance)` (libmgp applies it by the fused sweep, 8 columns per launch; DESIGN
+    4.15) and every product with K_mm is `ops.knm_matvec(spec, Z, Z, .)`; `K_mn [M, B]` of one batch stays dense, as
+    the reference holds it.  What returns or needs an [M, M] array is refused with `ValueError`: the exact trace of
+    `prior_kl` (`num_probes=None` without `probes`: M right-hand sides), `shared_inverse=True` (the explicit inverse)
+    and `logdet_gradient()` (dL/dK itself)."""
+
+    def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, matrix_free=False,
+                 **kwargs):
         super().__init__(kernel, likelihood, inducing_variable, **kwargs)
         self.conjugate_gradient = conjugate_gradient
         self.num_probes = num_probes
         self.probe_seed = 0
+        self.matrix_free = bool(matrix_free)
+
+    def _system(self):
+        """(K_mm or None, what the CG solves on, R [r, M] -> R K_mm): the two dense matrices and `ops.symm_matmul`, or
+        with `matrix_free` the operator and the K(Z, Z) sweep."""
+        if not self.matrix_free:
+            Kmm, KmmLambda = self._Kmm_and_KmmLambda()  # :300-301
+            return Kmm, KmmLambda, lambda R: ops.symm_matmul(Kmm, R)
+        Z = self.inducing_variable.Z
+        spec = self.kernel.spec(Z.shape[1])
+        op = KmmLambdaOperator(self.kernel, Z, self.diag_variance[:, 0].contiguous())
+        return None, op, lambda R: ops.knm_matvec(spec, Z, Z, R, ops.ROWS, ops.ROWS)
 
     def prior_kl(self, probes=None):  # :293-322
-        Kmm, KmmLambda = self._Kmm_and_KmmLambda()  # :300-301
+        if self.matrix_free and self.num_probes is None and probes is None:
+            raise ValueError("matrix_free=True needs num_probes (or probes=): the exact trace solves M right-hand sides")
+        Kmm, KmmLambda, times_kmm = self._system()
         cg = self.conjugate_gradient
         a = cg(KmmLambda, self.pseudo_u)  # :303
         if self.num_probes is None and probes is None:
             trace = cg(KmmLambda, Kmm).diagonal().sum().item()  # :305-306
         else:
             if probes is None:
-                probes = rademacher((Kmm.shape[0], self.num_probes), Kmm.dtype, Kmm.device, self.probe_seed)
+                Z = self.inducing_variable.Z
+                probes = rademacher((Z.shape[0], self.num_probes), Z.dtype, Z.device, self.probe_seed)
                 self.probe_seed += 1
             S = cg(KmmLambda, probes)  # :311
-            Kp = ops.symm_matmul(Kmm, probes.t().contiguous())  # (Kmm Zp)^T, :312
+            Kp = times_kmm(probes.t().contiguous())  # (Kmm Zp)^T, :312
             trace = ops.dot_all(S.t().contiguous(), Kp) / probes.shape[1]  # :313-314
         at = a.t().contiguous()
-        quad = ops.dot_all(ops.symm_matmul(Kmm, at), at)  # :316-317
+        quad = ops.dot_all(times_kmm(at), at)  # :316-317
         logdet = 0.0  # eval_logdet forward value, :319 -> :46
         const = torch.log(self.diag_variance).sum().item()  # :321
         return 0.5 * (quad - trace + logdet - const)  # :322
@@ -278,7 +301,7 @@ class CGGP(ClusterGP):
         iv, kernel = self.inducing_variable, self.kernel
         cg = self.conjugate_gradient
         if _shared is None:
-            _, KmmLambda = self._Kmm_and_KmmLambda()  # :333,337
+            _, KmmLambda, _ = self._system()  # :333,337
             a = cg(KmmLambda, self.pseudo_u)  # :339
         else:  # predict_f_batched: the N-free pieces are the same for every batch
             KmmLambda, a = _shared
@@ -302,7 +325,10 @@ class CGGP(ClusterGP):
         `iterations x 2 M^3 + 2 N M^2` flops instead of `iterations x 2 N M^2`.  The columns of I are
         solved to `inverse_threshold` (default: the model's threshold squared, so that the product
         with a batch stays inside the per-batch solve's own tolerance)."""
-        _, KmmLambda = self._Kmm_and_KmmLambda()
+        if shared_inverse and self.matrix_free:
+            raise ValueError("shared_inverse=True forms the [M, M] inverse; matrix_free=True refuses it "
+                             "(pass shared_inverse=False)")
+        _, KmmLambda, _ = self._system()
         cg = self.conjugate_gradient
         a = cg(KmmLambda, self.pseudo_u)
         means, variances = [], []
@@ -343,8 +369,14 @@ class CGGP(ClusterGP):
         evaluated once and counted once per batch, and the predictive moments of all rows come from
         `predict_f_batched` (with `shared_inverse`: one M-column CG for the whole data set instead of
         one B-column CG per batch).  With Hutchinson probes the reference draws fresh probes in every
-        batch's KL; here the one evaluation stands for all of them."""
+        batch's KL; here the one evaluation stands for all of them.
+
+        With `matrix_free=True` the default `shared_inverse=True` raises `ValueError` (the shared inverse is an [M, M]
+        array): pass `shared_inverse=False` there."""
         x, y = data
+        if shared_inverse and self.matrix_free:
+            raise ValueError("shared_inverse=True forms the [M, M] inverse; matrix_free=True refuses it "
+                             "(pass shared_inverse=False)")
         kl = self.prior_kl(probes=probes)
         mu, var = self.predict_f_batched(x, batch_size, shared_inverse=shared_inverse)
         ve = self.likelihood.variational_expectations(x, mu, var, y)
@@ -357,6 +389,9 @@ class CGGP(ClusterGP):
 
     def logdet_gradient(self, df=1.0, probes=None):
         """d/dK of the omitted log|Kmm+Lambda| term (`eval_logdet` backward, row M5)."""
+        if self.matrix_free:
+            raise ValueError("logdet_gradient() returns the [M, M] array dL/dK; matrix_free=True refuses it "
+                             "(TrainableCGGP(matrix_free=True) contracts it with dK/dtheta instead)")
         _, KmmLambda = self._Kmm_and_KmmLambda()
         return eval_logdet_grad(KmmLambda, self.conjugate_gradient, df, self.num_probes, probes,
                                 seed=self.probe_seed)

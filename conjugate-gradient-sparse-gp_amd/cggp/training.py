@@ -112,6 +112,101 @@ class _LogdetFromSolution(torch.autograd.Function):
         return (lv @ (df * probes).t()) / probes.shape[1], None, None
 
 
+def _frozen_kernel(kind, variance, lengthscales):
+    from . import kernels
+    cls = {"se": kernels.SquaredExponential, "matern12": kernels.Matern12, "matern32": kernels.Matern32,
+           "matern52": kernels.Matern52}[kind]
+    return cls(variance=float(variance), lengthscales=[float(v) for v in lengthscales.reshape(-1)])
+
+
+def _theta_grads(dvar, dls, v_shape, l_shape):
+    """(dvariance, dlengthscales) of a libmgp bilinear form as CPU tensors of the parameters' shapes (one shared
+    lengthscale collects the sum, as `_KBlock`)."""
+    n_l = int(np.prod(l_shape)) if len(l_shape) else 1
+    gl = torch.tensor(dls if n_l > 1 else [sum(dls)], dtype=torch.float64).reshape(l_shape)
+    return torch.tensor(dvar, dtype=torch.float64).reshape(v_shape), gl
+
+
+class _KzzTimes(torch.autograd.Function):
+    """k(Z, Z) V for V [M, R], K never formed: forward `mgp_knm_matvec` on (Z, Z); backward dV = k(Z, Z) G and
+    (dvariance, dlengthscales) = sum_r g_r^T (dK/dtheta) v_r by `mgp_kxx_grad`."""
+
+    @staticmethod
+    def forward(ctx, variance, lengthscales, Z, V, kind):
+        ctx.spec = ops.KernelSpec(kind, float(variance), [float(x) for x in lengthscales.reshape(-1)], Z.shape[1])
+        ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
+        V = V.contiguous()
+        ctx.save_for_backward(Z, V)
+        return ops.knm_matvec(ctx.spec, Z, Z, V)
+
+    @staticmethod
+    def backward(ctx, G):
+        Z, V = ctx.saved_tensors
+        G = G.contiguous()
+        gv, gl = _theta_grads(*ops.kxx_grad(ctx.spec, Z, G, V), ctx.v_shape, ctx.l_shape)
+        dV = ops.knm_matvec(ctx.spec, Z, Z, G) if ctx.needs_input_grad[3] else None
+        return gv, gl, None, dV, None
+
+
+class _KzzLambdaSolve(torch.autograd.Function):
+    """X = (k(Z, Z) + diag lam)^-1 rhs for rhs [M, R] by the device CG on `KmmLambdaOperator`.  Backward, with
+    Gb = (k(Z, Z) + diag lam)^-1 G (`_adjoint_solve`: the shortcut and the warm start of `_CGFunction` where they
+    apply): d rhs = Gb, (dvariance, dlengthscales) = -sum_r gb_r^T (dK/dtheta) x_r (`mgp_kxx_grad`),
+    dlam = -sum_r Gb o X."""
+
+    @staticmethod
+    def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg):
+        from .conjugate_gradient import KmmLambdaOperator, _solve_device
+        kern = _frozen_kernel(kind, variance, lengthscales)
+        ctx.op = KmmLambdaOperator(kern, Z, lam.detach().contiguous())
+        ctx.cfg = cg.config(Z.shape[0])
+        ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
+        rows = rhs.detach().t().contiguous()
+        sol, _, err = _solve_device(ctx.op, rows, None, *ctx.cfg)
+        ctx.save_for_backward(sol, rows, err)
+        return sol.t().contiguous()
+
+    @staticmethod
+    def backward(ctx, G):
+        from .conjugate_gradient import _adjoint_solve
+        sol, rows, err = ctx.saved_tensors
+        op = ctx.op
+        Gb = _adjoint_solve(op, sol, rows, err, G.t().contiguous(), ctx.cfg, True).contiguous()
+        dvar, dls = ops.kxx_grad(op.spec, op.Z, Gb, sol, ops.ROWS)
+        gv, gl = _theta_grads(-dvar, [-v for v in dls], ctx.v_shape, ctx.l_shape)
+        return gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), None, None, None
+
+
+class _KzzLambdaLogdet(torch.autograd.Function):
+    """`eval_logdet` on the operator: value 0.0; backward (dvariance, dlengthscales) = df sum_r s_r^T (dK/dtheta) z_r / P
+    and dlam = df sum_r S o Zp / P, with S = (k(Z, Z) + diag lam)^-1 Zp handed in (the trace estimator's solve, reused)
+    or, when `solution` is None, solved in the backward pass as the reference does (`cggp/models.py:38-41`)."""
+
+    @staticmethod
+    def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg):
+        ctx.kind, ctx.cg, ctx.have = kind, cg, solution is not None
+        ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
+        ctx.theta = (float(variance), lengthscales.detach().clone())
+        ctx.save_for_backward(lam.detach(), probes, Z, *((solution,) if ctx.have else ()))
+        return torch.zeros((), dtype=Z.dtype, device=Z.device)
+
+    @staticmethod
+    def backward(ctx, df):
+        from .conjugate_gradient import KmmLambdaOperator
+        lam, probes, Z = ctx.saved_tensors[:3]
+        kern = _frozen_kernel(ctx.kind, *ctx.theta)
+        if ctx.have:
+            S = ctx.saved_tensors[3]
+        else:
+            with torch.no_grad():
+                S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous()), probes)
+        P = probes.shape[1]
+        scale = float(df) / P
+        dvar, dls = ops.kxx_grad(kern.spec(Z.shape[1]), Z, S.contiguous(), probes.contiguous())
+        gv, gl = _theta_grads(scale * dvar, [scale * v for v in dls], ctx.v_shape, ctx.l_shape)
+        return gv, gl, scale * (S * probes).sum(dim=1), None, None, None, None, None
+
+
 class TrainableCGGP:
     """Differentiable `CGGP.elbo` (`cggp/models.py:125-134,293-354`).
 
@@ -120,10 +215,16 @@ class TrainableCGGP:
     `fused_solves=True` additionally sends `pseudo_u`, `Kmn` and the probes through ONE device CG as
     columns of one right-hand side; measured slower at C2 sizes (72.9 vs 67.2 ms per Adam step)
     because the reference's "any column not converged" stopping rule then makes the 1000-column
-    GEMM-regime solve run as long as the slowest (Rademacher) columns, so it is off by default."""
+    GEMM-regime solve run as long as the slowest (Rademacher) columns, so it is off by default.
+
+    `matrix_free=True`: the same ELBO with K_mm never formed, at any M.  The Z-Z block enters through three autograd
+    nodes -- `_KzzTimes` (k(Z, Z) V), `_KzzLambdaSolve` (the device CG on `KmmLambdaOperator`) and `_KzzLambdaLogdet` --
+    whose backward passes contract dL/dK with dK/dtheta by `mgp_kxx_grad`; the [M, B] block of a batch keeps `_KBlock`.
+    The exact trace (`num_probes=None` without `probes`) needs M right-hand sides and raises `ValueError`.
+    `fused_solves=True` works there too: one operator solve on the columns [pseudo_u, K_mn, probes]."""
 
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
-                 num_data=None, fused_solves=False, independent_logdet_probes=False):
+                 num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False):
         self.kernel = kernel if isinstance(kernel, TrainableKernel) else TrainableKernel(kernel)
         self.noise_p = Parameter(noise_variance)
         self.Z = Z
@@ -140,11 +241,55 @@ class TrainableCGGP:
         # two estimates are then correlated
         self.independent_logdet_probes = bool(independent_logdet_probes)
         self.logdet_probe_seed = 1 << 20
+        self.matrix_free = bool(matrix_free)
 
     def parameters(self):
         return self.kernel.parameters() + [self.noise_p.raw]
 
+    def _elbo_matrix_free(self, data, probes):
+        x, y = data
+        Z, cg, kind = self.Z, self.conjugate_gradient, self.kernel.name
+        dev, dt, M = Z.device, Z.dtype, Z.shape[0]
+        if self.num_probes is None and probes is None:
+            raise ValueError("matrix_free=True needs num_probes (or probes=): the exact trace solves M right-hand sides")
+        s2 = self.noise_p().to(device=dev, dtype=dt)
+        var_p, ls = self.kernel.variance_p(), self.kernel.lengthscales_p()
+        if ls.dim() == 0:
+            ls = ls.reshape(1)
+        var_f = var_p.to(device=dev, dtype=dt)
+        lam = s2 / self.cluster_counts[:, 0]  # diag_variance, :226-228
+        Kmn = self.kernel.K(Z, x)  # :334
+        if probes is None:
+            probes = rademacher((M, self.num_probes), dt, dev, self.probe_seed)
+            self.probe_seed += 1
+        P = probes.shape[1]
+        times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind)
+        solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg)
+        if self.fused_solves:
+            B = Kmn.shape[1]
+            sol = solve(torch.cat([self.pseudo_u, Kmn, probes], dim=1))  # :303, :339, :311 in one solve
+            a, W, S = sol[:, :1], sol[:, 1:1 + B], sol[:, 1 + B:]
+        else:
+            a, W, S = solve(self.pseudo_u), solve(Kmn), solve(probes)  # :303 / :339, :340, :311
+        fvar = (var_f - (Kmn * W).sum(dim=0))[:, None]  # :343-345
+        fmu = Kmn.t() @ a  # :351
+        var_exp = -0.5 * math.log(2.0 * math.pi) - 0.5 * torch.log(s2) - 0.5 * ((y - fmu) ** 2 + fvar) / s2
+        trace = (S * times_kzz(probes)).sum() / P  # :312-314
+        quad = (times_kzz(a) * a).sum()  # :316-317
+        if self.independent_logdet_probes:
+            own = rademacher((M, P), dt, dev, self.logdet_probe_seed)  # fresh draw, :38-39
+            self.logdet_probe_seed += 1
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None, own, Z, kind, cg)  # solved in the backward pass
+        else:
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, S.detach(), probes, Z, kind, cg)  # K^-1 Zp reused
+        const = torch.log(lam).sum()  # :321
+        kl = 0.5 * (quad - trace + logdet - const)
+        scale = 1.0 if self.num_data is None else float(self.num_data) / float(x.shape[0])  # :163-169
+        return var_exp.sum() * scale - kl
+
     def elbo(self, data, probes=None):
+        if self.matrix_free:
+            return self._elbo_matrix_free(data, probes)
         x, y = data
         dev, dt = self.Z.device, self.Z.dtype
         cg = self.conjugate_gradient
@@ -203,7 +348,7 @@ class TrainableCGGP:
         from .models import CGGP
         return CGGP(self.kernel.frozen(), self.noise_p.value, self.Z, self.conjugate_gradient,
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
-                    num_data=self.num_data)
+                    num_data=self.num_data, matrix_free=self.matrix_free)
 
 
 class _GPRLmlEstimate(torch.autograd.Function):
