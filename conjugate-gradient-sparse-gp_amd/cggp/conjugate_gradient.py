@@ -40,6 +40,10 @@ class LinearOperator:
         """(MgpOperator, keepalive objects)"""
         raise NotImplementedError
 
+    def _struct_for(self, columns):
+        """`_struct()` for a solve or product with `columns` right-hand sides (operators whose form depends on it)."""
+        return self._struct()
+
     def rmatmul(self, P):
         """P [Bt,n] @ Op -> [Bt,n] (the layout of `state.p @ A`, reference :65)."""
         P = _hip.check_tensor(P, "P", dtype=self.dtype)
@@ -49,7 +53,7 @@ class LinearOperator:
         if P.shape[0] == 0:
             return out
         hd = _hip.get_handle(self.device)
-        st, keep = self._struct()
+        st, keep = self._struct_for(P.shape[0])
         hd.check(hd.lib.mgp_operator_apply(hd.h, ctypes.byref(st), _hip.ptr(P), P.shape[0], _hip.ptr(out)))
         del keep
         return out
@@ -92,10 +96,38 @@ class DenseOperator(LinearOperator):
         return self.A
 
 
-class KmmLambdaOperator(LinearOperator):
-    """(k(Z,Z) + diag(lam)) applied matrix-free (row M2, matrix-free alternative)."""
+# `wide="auto"` takes the many-column form from these sizes on: at every measured point with at least that many columns
+# and that M it took at most 0.9 of the sweep form's best time, for both measured kernel configurations, one application
+# and a 20-step solve alike; no smaller width does at any M (at 32 columns the SE solve at M = 2^17 is at 0.91).
+# 2^12 is the smallest M measured (profiles/kmm_wide_times.json)
+WIDE_MIN_COLUMNS = 48
+WIDE_MIN_M = 1 << 12
+WIDE_MAX_D = 32  # MGP_FUSED_MAX_D: above it, and in fp32, libmgp applies the sweep form whatever the kind
 
-    def __init__(self, kernel, Z, lam):
+
+def check_wide(wide, name="wide"):
+    """`wide` / `wide_solves` as given, or `ValueError`: False, True or "auto"."""
+    if isinstance(wide, bool) or (isinstance(wide, str) and wide == "auto"):
+        return wide
+    raise ValueError(f"{name} must be False, True or 'auto', got {wide!r}")
+
+
+def wide_auto(dtype, D, columns, M):
+    """The rule behind `wide="auto"`: fp64, D <= 32, at least WIDE_MIN_COLUMNS columns and M >= WIDE_MIN_M."""
+    return (dtype == torch.float64 and int(D) <= WIDE_MAX_D and int(columns) >= WIDE_MIN_COLUMNS
+            and int(M) >= WIDE_MIN_M)
+
+
+class KmmLambdaOperator(LinearOperator):
+    """(k(Z,Z) + diag(lam)) applied matrix-free (row M2, matrix-free alternative).
+
+    `wide=False`: libmgp's fused sweep, 8 right-hand sides per launch (`MGP_OP_KMM_LAMBDA`).  `wide=True`: the
+    many-column form (`MGP_OP_KMM_LAMBDA_WIDE`: each kernel value evaluated once per 256 right-hand sides and contracted
+    on the fp64 matrix cores; fp32 and D > 32 take the sweep form inside libmgp).  `wide="auto"`: the many-column form
+    iff `wide_auto(dtype, D, columns, M)`, decided per solve or product, where the column count is known."""
+
+    def __init__(self, kernel, Z, lam, wide=False):
+        self.wide = check_wide(wide)
         self.Z = _hip.check_tensor(Z, "Z")
         self.lam = _hip.check_tensor(lam, "lam", dtype=self.Z.dtype).reshape(-1)
         M = self.Z.shape[0]
@@ -107,10 +139,20 @@ class KmmLambdaOperator(LinearOperator):
         self.dtype = self.Z.dtype
         self.device = self.Z.device
 
+    def kind_for(self, columns):
+        """The operator kind libmgp is handed for `columns` right-hand sides."""
+        wide = self.wide
+        if wide == "auto":
+            wide = wide_auto(self.dtype, self.Z.shape[1], columns, self.shape[0])
+        return _hip.OP_KMM_LAMBDA_WIDE if wide else _hip.OP_KMM_LAMBDA
+
     def _struct(self):
+        return self._struct_for(0)
+
+    def _struct_for(self, columns):
         k = self.spec.struct(_hip.dtype_code(self.Z))
         st = _hip.MgpOperator()
-        st.kind = _hip.OP_KMM_LAMBDA
+        st.kind = self.kind_for(columns)
         st.dtype = k.dtype
         st.n = self.shape[0]
         st.kernel = ctypes.pointer(k)
@@ -647,7 +689,7 @@ def _solve_device(op, rhs, initial_solution, error_threshold, preconditioner, ma
         if isinstance(op, SgprNormalOperator):
             op.reserve(Bt)
         hd = _hip.get_handle(op.device)
-        st, keep = op._struct()
+        st, keep = op._struct_for(Bt)
         pst, pkeep = preconditioner._native_for(op, Bt)
         hd.check(hd.lib.mgp_pcg_solve(
             hd.h, ctypes.byref(st), ctypes.byref(pst), _hip.ptr(rhs), _hip.ptr(v0), Bt,

@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from .conjugate_gradient import (ConjugateGradient, KmmLambdaOperator, KxxNoiseOperator, PivotedCholeskyPreconditioner,
-                                 SgprNormalOperator, SubsampledNormalPreconditioner)
+                                 SgprNormalOperator, SubsampledNormalPreconditioner, check_wide)
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
 from .slq import slq_log_quadratic
@@ -253,10 +253,19 @@ class CGGP(ClusterGP):
     4.15) and every product with K_mm is `ops.knm_matvec(spec, Z, Z, .)`; `K_mn [M, B]` of one batch stays dense, as
     the reference holds it.  What returns or needs an [M, M] array is refused with `ValueError`: the exact trace of
     `prior_kl` (`num_probes=None` without `probes`: M right-hand sides), `shared_inverse=True` (the explicit inverse)
-    and `logdet_gradient()` (dL/dK itself)."""
+    and `logdet_gradient()` (dL/dK itself).
+
+    `wide_solves` (with `matrix_free=True` only; anything but False without it is a `ValueError`) is the `wide`
+    argument of every `KmmLambdaOperator` the model makes: False the sweep form, True libmgp's many-column form
+    (each kernel value evaluated once per 256 columns and contracted on the fp64 matrix cores: the form for
+    `W = CG(K_mm + Lambda, K_mn)`, one column per test row), "auto" the many-column form from
+    `conjugate_gradient.WIDE_MIN_COLUMNS` columns and `WIDE_MIN_M` inducing points on."""
 
     def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, matrix_free=False,
-                 **kwargs):
+                 wide_solves=False, **kwargs):
+        self.wide_solves = check_wide(wide_solves, "wide_solves")
+        if self.wide_solves is not False and not matrix_free:
+            raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
         super().__init__(kernel, likelihood, inducing_variable, **kwargs)
         self.conjugate_gradient = conjugate_gradient
         self.num_probes = num_probes
@@ -271,7 +280,7 @@ class CGGP(ClusterGP):
             return Kmm, KmmLambda, lambda R: ops.symm_matmul(Kmm, R)
         Z = self.inducing_variable.Z
         spec = self.kernel.spec(Z.shape[1])
-        op = KmmLambdaOperator(self.kernel, Z, self.diag_variance[:, 0].contiguous())
+        op = KmmLambdaOperator(self.kernel, Z, self.diag_variance[:, 0].contiguous(), wide=self.wide_solves)
         return None, op, lambda R: ops.knm_matvec(spec, Z, Z, R, ops.ROWS, ops.ROWS)
 
     def prior_kl(self, probes=None):  # :293-322

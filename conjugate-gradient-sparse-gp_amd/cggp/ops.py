@@ -220,7 +220,7 @@ def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e
     stats = _hip.MgpCgStats()
     if Bt > 0:
         hd = _hip.get_handle(op.device)
-        st, keep = op._struct()
+        st, keep = op._struct_for(Bt)
         if preconditioner is None:
             pre, pkeep = _hip.MgpPrecond(), ()
             pre.kind = _hip.PRE_EYE

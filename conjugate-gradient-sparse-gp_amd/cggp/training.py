@@ -155,10 +155,10 @@ class _KzzLambdaSolve(torch.autograd.Function):
     dlam = -sum_r Gb o X."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg):
+    def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg, wide=False):
         from .conjugate_gradient import KmmLambdaOperator, _solve_device
         kern = _frozen_kernel(kind, variance, lengthscales)
-        ctx.op = KmmLambdaOperator(kern, Z, lam.detach().contiguous())
+        ctx.op = KmmLambdaOperator(kern, Z, lam.detach().contiguous(), wide=wide)
         ctx.cfg = cg.config(Z.shape[0])
         ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
         rows = rhs.detach().t().contiguous()
@@ -174,7 +174,8 @@ class _KzzLambdaSolve(torch.autograd.Function):
         Gb = _adjoint_solve(op, sol, rows, err, G.t().contiguous(), ctx.cfg, True).contiguous()
         dvar, dls = ops.kxx_grad(op.spec, op.Z, Gb, sol, ops.ROWS)
         gv, gl = _theta_grads(-dvar, [-v for v in dls], ctx.v_shape, ctx.l_shape)
-        return gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), None, None, None
+        grads = (gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), None, None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `wide` is optional in apply()
 
 
 class _KzzLambdaLogdet(torch.autograd.Function):
@@ -183,8 +184,8 @@ class _KzzLambdaLogdet(torch.autograd.Function):
     or, when `solution` is None, solved in the backward pass as the reference does (`cggp/models.py:38-41`)."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg):
-        ctx.kind, ctx.cg, ctx.have = kind, cg, solution is not None
+    def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg, wide=False):
+        ctx.kind, ctx.cg, ctx.have, ctx.wide = kind, cg, solution is not None, wide
         ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
         ctx.theta = (float(variance), lengthscales.detach().clone())
         ctx.save_for_backward(lam.detach(), probes, Z, *((solution,) if ctx.have else ()))
@@ -199,12 +200,13 @@ class _KzzLambdaLogdet(torch.autograd.Function):
             S = ctx.saved_tensors[3]
         else:
             with torch.no_grad():
-                S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous()), probes)
+                S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous(), wide=ctx.wide), probes)
         P = probes.shape[1]
         scale = float(df) / P
         dvar, dls = ops.kxx_grad(kern.spec(Z.shape[1]), Z, S.contiguous(), probes.contiguous())
         gv, gl = _theta_grads(scale * dvar, [scale * v for v in dls], ctx.v_shape, ctx.l_shape)
-        return gv, gl, scale * (S * probes).sum(dim=1), None, None, None, None, None
+        grads = (gv, gl, scale * (S * probes).sum(dim=1), None, None, None, None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `wide` is optional in apply()
 
 
 class TrainableCGGP:
@@ -221,10 +223,17 @@ class TrainableCGGP:
     nodes -- `_KzzTimes` (k(Z, Z) V), `_KzzLambdaSolve` (the device CG on `KmmLambdaOperator`) and `_KzzLambdaLogdet` --
     whose backward passes contract dL/dK with dK/dtheta by `mgp_kxx_grad`; the [M, B] block of a batch keeps `_KBlock`.
     The exact trace (`num_probes=None` without `probes`) needs M right-hand sides and raises `ValueError`.
-    `fused_solves=True` works there too: one operator solve on the columns [pseudo_u, K_mn, probes]."""
+    `fused_solves=True` works there too: one operator solve on the columns [pseudo_u, K_mn, probes].
+    `wide_solves` (False, True or "auto"; with `matrix_free=True` only) is handed to every `KmmLambdaOperator`, as in
+    `models.CGGP`."""
 
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
-                 num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False):
+                 num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
+                 wide_solves=False):
+        from .conjugate_gradient import check_wide
+        self.wide_solves = check_wide(wide_solves, "wide_solves")
+        if self.wide_solves is not False and not matrix_free:
+            raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
         self.kernel = kernel if isinstance(kernel, TrainableKernel) else TrainableKernel(kernel)
         self.noise_p = Parameter(noise_variance)
         self.Z = Z
@@ -264,7 +273,8 @@ class TrainableCGGP:
             self.probe_seed += 1
         P = probes.shape[1]
         times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind)
-        solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg)
+        wide = self.wide_solves
+        solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide)
         if self.fused_solves:
             B = Kmn.shape[1]
             sol = solve(torch.cat([self.pseudo_u, Kmn, probes], dim=1))  # :303, :339, :311 in one solve
@@ -279,9 +289,9 @@ class TrainableCGGP:
         if self.independent_logdet_probes:
             own = rademacher((M, P), dt, dev, self.logdet_probe_seed)  # fresh draw, :38-39
             self.logdet_probe_seed += 1
-            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None, own, Z, kind, cg)  # solved in the backward pass
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None, own, Z, kind, cg, wide)  # solved in the backward pass
         else:
-            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, S.detach(), probes, Z, kind, cg)  # K^-1 Zp reused
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, S.detach(), probes, Z, kind, cg, wide)  # K^-1 Zp reused
         const = torch.log(lam).sum()  # :321
         kl = 0.5 * (quad - trace + logdet - const)
         scale = 1.0 if self.num_data is None else float(self.num_data) / float(x.shape[0])  # :163-169
@@ -348,7 +358,7 @@ class TrainableCGGP:
         from .models import CGGP
         return CGGP(self.kernel.frozen(), self.noise_p.value, self.Z, self.conjugate_gradient,
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
-                    num_data=self.num_data, matrix_free=self.matrix_free)
+                    num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves)
 
 
 class _GPRLmlEstimate(torch.autograd.Function):

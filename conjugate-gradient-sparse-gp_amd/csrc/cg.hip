@@ -413,6 +413,10 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
   switch (op->kind) {
     case MGP_OP_DENSE:
       return mgp_symm_matmul_gated(h, op->dtype, op->A, n, P, Bt, out, gate, loc);
+    case MGP_OP_KMM_LAMBDA_WIDE:  // the many-column form (project.hip); fp32 and D > 32 take the sweep form below
+      if (mgp_kmm_wide_serves(op->kernel))
+        return mgp_kmm_wide_apply(h, op->kernel, op->Z, op->M, op->lambda, P, Bt, out, gate);
+      [[fallthrough]];
     case MGP_OP_KMM_LAMBDA: {
       MGP_TRY(mgp_sweep(h, op->kernel, op->Z, op->M, op->Z, op->M, VecView{P, 1, n}, (int)Bt,
                         VecViewMut{out, 1, n}, 0.0, VecView{nullptr, 0, 0}, gate));
@@ -527,13 +531,13 @@ int check_operator(mgp_handle* h, const mgp_operator* op) {
   if (op->n <= 0) return mgp_fail(h, MGP_E_SHAPE, "operator n must be > 0");
   if (op->kind == MGP_OP_DENSE) {
     if (!op->A) return mgp_fail(h, MGP_E_BADARG, "dense operator without matrix");
-  } else if (op->kind == MGP_OP_SGPR || op->kind == MGP_OP_KMM_LAMBDA) {
+  } else if (op->kind == MGP_OP_SGPR || op->kind == MGP_OP_KMM_LAMBDA || op->kind == MGP_OP_KMM_LAMBDA_WIDE) {
     MGP_TRY(mgp_check_kernel(h, op->kernel));
     if (op->kernel->dtype != op->dtype) return mgp_fail(h, MGP_E_DTYPE, "operator/kernel dtype mismatch");
     if (op->M != op->n || !op->Z) return mgp_fail(h, MGP_E_SHAPE, "operator needs Z with M == n");
     if (op->kind == MGP_OP_SGPR && (!op->Kmm || op->N < 0 || (op->N > 0 && !op->X)))
       return mgp_fail(h, MGP_E_BADARG, "SGPR operator needs X and Kmm");
-    if (op->kind == MGP_OP_KMM_LAMBDA && !op->lambda) return mgp_fail(h, MGP_E_BADARG, "needs lambda");
+    if (op->kind != MGP_OP_SGPR && !op->lambda) return mgp_fail(h, MGP_E_BADARG, "needs lambda");
     if (op->kind == MGP_OP_SGPR && op->allreduce && op->comm)
       return mgp_fail(h, MGP_E_BADARG, "give either the allreduce hook or a communicator, not both");
     if (op->kind == MGP_OP_SGPR && op->allreduce && op->world_size < 1)
@@ -874,6 +878,12 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
                 /*check_every=*/check_every < 1 ? 1L : (long)check_every, /*coef_steps=*/coef_steps,
                 /*thr=*/thr, /*min_float=*/min_float, /*V=*/V, /*err_out=*/err_out, /*coef=*/coef, /*s=*/h->stream,
                 /*pre=*/pc, /*a=*/arena, /*z=*/pc.cb ? (T*)pc.cb->cb_z : arena.z, /*dense1=*/dense1, /*fused=*/fused};
+  // many-column (K_mm + Lambda): the arena for the widest group and the pack of Z before the loop, nothing inside it
+  WideHold wide_hold(h);
+  if (op->kind == MGP_OP_KMM_LAMBDA_WIDE && mgp_kmm_wide_serves(op->kernel)) {
+    MGP_TRY(mgp_kmm_wide_prepare(h, op->kernel, op->Z, op->M, Bt, nullptr));
+    wide_hold.hold(op->Z, op->M);
+  }
   MGP_TRY(cg.start(V0, persist));
   MGP_TRY(persist ? cg.run_persist() : (dense1 && h->poll_pipeline) ? cg.run_dense1_pipelined() : cg.run_polled());
   return cg.statistics(stats, t0);

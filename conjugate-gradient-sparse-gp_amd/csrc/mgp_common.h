@@ -46,6 +46,10 @@ struct mgp_handle {
   // route, R^T, one row panel of k(Xs, X) and one chunk of the product
   void* prj = nullptr;
   size_t prj_bytes = 0;
+  // many-column (K_mm + Lambda) operator (MGP_OP_KMM_LAMBDA_WIDE, project.hip): the Z whose pack stands at the front of
+  // prj for the solve under way (WideHold); null outside a solve, where every application packs for itself
+  const void* wide_pack_src = nullptr;
+  long wide_pack_m = 0;
   // generic-D scratch (transposed multipliers, kernel panel, chunk output)
   void* gen = nullptr;
   size_t gen_bytes = 0;
@@ -151,6 +155,21 @@ struct PackHold {
     h->pack_hold = false;
     h->pack[0].valid = h->pack[1].valid = false;
   }
+};
+
+// scope guard of mgp_pcg_solve on MGP_OP_KMM_LAMBDA_WIDE: Z is packed once, before the loop, and held until the solve ends
+struct WideHold {
+  mgp_handle* h;
+  explicit WideHold(mgp_handle* hh) : h(hh) { release(); }
+  void hold(const void* Z, long M) {
+    h->wide_pack_src = Z;
+    h->wide_pack_m = M;
+  }
+  void release() {
+    h->wide_pack_src = nullptr;
+    h->wide_pack_m = 0;
+  }
+  ~WideHold() { release(); }
 };
 
 constexpr int MGP_PROF_CLK_WORDS = 64;        // per profiled launch: 16 slots x (real0, clk0, real1, clk1)
@@ -397,6 +416,13 @@ int mgp_sweep(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, con
 // kxx.hip: out(i,r) = variance * sum_j k(x_i, x_j) v(j,r) + s2 v(i,r), each unordered pair evaluated once
 int mgp_kxx(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, VecView V, int32_t R,
             VecViewMut out, const int* gate);
+// project.hip: the many-column form of out[Bt, M] = P[Bt, M] (k(Z, Z) + diag lambda), fp64 and D <= MGP_FUSED_MAX_D
+// (mgp_kmm_wide_serves).  prepare reserves the prj arena for Bt right-hand sides and packs Z at its front; apply packs
+// for itself unless a WideHold names this Z.  gate: device int, every kernel of the route skips if 0
+bool mgp_kmm_wide_serves(const mgp_kernel* k);
+int mgp_kmm_wide_prepare(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, int64_t Bt, const int* gate);
+int mgp_kmm_wide_apply(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, const void* lambda, const void* P,
+                       int64_t Bt, void* out, const int* gate);
 // generic-D forms (generic.hip): explicit panels + NT GEMM, any D <= MGP_MAX_D
 int mgp_k_dense_generic(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
                         void* out, int64_t ld, double jitter, const void* diag_add, const int* gate);

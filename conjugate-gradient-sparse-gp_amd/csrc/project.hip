@@ -28,9 +28,23 @@ constexpr long PJ_CHUNK_B = 1L << 16;  // test rows per launch (bounds the parti
 
 // Xp[i] = (2 x_i / l, -|x_i / l|^2): the streamed side of the expansion-form distance, packed once per call so that a
 // step of the main kernel stages its 16 rows with one flat copy
-template <int DP>
+// No gate, or the gate word of a CG solve (MGP_OP_KMM_LAMBDA_WIDE): the last argument of the two kernels below.  An
+// empty argument generates no code, so the mgp_knm_project instantiations keep the instruction streams they had before
+// the gate existed (a null pointer tested at run time moved that entry point's times by up to 1 % either way).
+struct PjNoGate {};
+struct PjCgGate {
+  const int* word;  // device int: 0 = closed, the kernel reads and writes nothing; may be null (open)
+};
+template <typename GATE>
+__device__ __forceinline__ bool pj_closed(GATE gate) {
+  if constexpr (std::is_same<GATE, PjCgGate>::value) return gate.word != nullptr && *gate.word == 0;
+  return false;
+}
+
+template <int DP, typename GATE>
 __global__ __launch_bounds__(256) void pj_pack_kernel(const double* __restrict__ X, long N, int D, SweepParams prm,
-                                                      double* __restrict__ Xp) {
+                                                      double* __restrict__ Xp, GATE gate) {
+  if (pj_closed(gate)) return;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   double s = 0;
@@ -50,12 +64,13 @@ __global__ __launch_bounds__(256) void pj_pack_kernel(const double* __restrict__
 // tiles.  The next step's panels of R and X are fetched into registers before the current step's arithmetic and
 // stored to LDS after it, so their latency hides behind the VALU and MFMA work.  NQ <= 4 double-buffers the staged
 // panels (two barriers per step); NQ = 8 keeps one set (three barriers) to stay inside 64 KB of static LDS.
-template <int DP, int KIND, int MT, int NQ>
+template <int DP, int KIND, int MT, int NQ, typename GATE>
 __global__ __launch_bounds__(256) void knm_project_kernel(const double* __restrict__ Xs, long B,
                                                           const double* __restrict__ Xp, long N,
                                                           const double* __restrict__ R, long r_si, long r_sj, int r,
                                                           double* __restrict__ part, long rows_per_split, int D, int RP,
-                                                          SweepParams prm) {
+                                                          SweepParams prm, GATE gate) {
+  if (pj_closed(gate)) return;  // uniform
   constexpr int PB = 32 * MT;        // test rows per workgroup
   constexpr int KE = PK * PB / 256;  // kernel values per thread and step
   constexpr int RC = 32 * NQ;        // padded columns of this instantiation
@@ -272,7 +287,8 @@ int project_fused_dp(mgp_handle* h, const mgp_kernel* k, const double* Xs, long 
   MGP_TRY(mgp_reserve(h, &h->prj, &h->prj_bytes, part_bytes + (size_t)N * (DP + 1) * sizeof(double)));
   double* part = (double*)h->prj;
   double* Xp = (double*)((char*)h->prj + part_bytes);
-  hipLaunchKernelGGL((pj_pack_kernel<DP>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, X, N, D, prm, Xp);
+  hipLaunchKernelGGL((pj_pack_kernel<DP, PjNoGate>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, X, N, D, prm,
+                     Xp, PjNoGate{});
   MGP_LAUNCH_CHECK(h);
   for (long c0 = 0; c0 < B; c0 += PJ_CHUNK_B) {
     const long Bc = B - c0 < PJ_CHUNK_B ? B - c0 : PJ_CHUNK_B;
@@ -282,8 +298,8 @@ int project_fused_dp(mgp_handle* h, const mgp_kernel* k, const double* Xs, long 
     const double* xs = Xs + c0 * D;
     dim3 grid((unsigned)tiles, 1, (unsigned)ns);
 #define MGP_PJ(MTV, NQV)                                                                                             \
-  hipLaunchKernelGGL((knm_project_kernel<DP, KIND, MTV, NQV>), grid, dim3(256), 0, h->stream, xs, Bc, (const double*)Xp, \
-                     N, R, r_si, r_sj, r, part, rw, D, RP, prm)
+  hipLaunchKernelGGL((knm_project_kernel<DP, KIND, MTV, NQV, PjNoGate>), grid, dim3(256), 0, h->stream, xs, Bc,           \
+                     (const double*)Xp, N, R, r_si, r_sj, r, part, rw, D, RP, prm, PjNoGate{})
     if (r <= 32) MGP_PJ(4, 1);
     else if (r <= 64) MGP_PJ(4, 2);
     else if (r <= 128) MGP_PJ(4, 4);
@@ -337,7 +353,149 @@ int project_generic(mgp_handle* h, const mgp_kernel* k, const T* Xs, long B, con
   return MGP_OK;
 }
 
+// ---------------------------------------------------------------- many-column (k(Z, Z) + diag lambda) (MGP_OP_KMM_LAMBDA_WIDE)
+// out[Bt, M] = P[Bt, M] (k(Z, Z) + diag lambda) with the kernel above: Xs = Z, the packed Z streamed, R = P in the
+// MGP_ROWS layout, the right-hand sides in groups of at most PJ_MAX_R.  Every kernel value is evaluated once per group,
+// not once per 8 right-hand sides as by the sweep.  The arena: the pack of Z first (its place does not depend on the
+// group width, so one pack serves a whole solve), the split tiles of the widest group behind it.
+
+constexpr int FT_I = 64;  // output rows (elements of one right-hand side) per workgroup of the finish kernel
+constexpr int FT_B = 16;  // right-hand sides per workgroup: every padded width RP is a multiple
+
+// out[b, i] = variance * sum_split part[split][i][b] (split order) + lam[i] * P[b, i] for the rows i < rows of one row
+// chunk and the right-hand sides b < cols of one group; lam, P and out point at the chunk's first row and the group's
+// first right-hand side.  part is b-fastest, out is i-fastest: a 64 x 16 tile goes through LDS, read as 16-element
+// (128-byte) runs of part and written as 64-element runs of out.  No atomics; a closed gate writes nothing.
+__global__ __launch_bounds__(256) void kmm_wide_finish_kernel(const double* __restrict__ part, int nsplit, long Bpad,
+                                                              int RP, long rows, int cols, double variance,
+                                                              const double* __restrict__ lam,
+                                                              const double* __restrict__ P, double* __restrict__ out,
+                                                              long M, const int* __restrict__ gate) {
+  if (gate != nullptr && *gate == 0) return;
+  __shared__ double tile[FT_B][FT_I + 1];
+  const int t = threadIdx.x;
+  const long i0 = (long)blockIdx.x * FT_I;
+  const int bb = blockIdx.y * FT_B;
+  {
+    const int b = t & (FT_B - 1), il = t / FT_B;
+#pragma unroll
+    for (int u = 0; u < FT_I * FT_B / 256; ++u) {
+      const int ii = il + (256 / FT_B) * u;
+      const long i = i0 + ii;
+      double s = 0;
+      if (i < rows && bb + b < cols) {
+        for (int z = 0; z < nsplit; ++z) s += part[((long)z * Bpad + i) * RP + bb + b];
+        s *= variance;
+      }
+      tile[b][ii] = s;
+    }
+  }
+  __syncthreads();
+  const int ii = t & (FT_I - 1), bl = t / FT_I;
+  const long i = i0 + ii;
+  if (i >= rows) return;
+  const double l = lam[i];
+#pragma unroll
+  for (int u = 0; u < FT_I * FT_B / 256; ++u) {
+    const int b = bl + (256 / FT_I) * u;
+    if (bb + b < cols) {
+      const long e = (long)(bb + b) * M + i;
+      out[e] = mgp_fma(l, P[e], tile[b][ii]);
+    }
+  }
+}
+
+inline int wide_dp(int D) { return D <= 2 ? 2 : D <= 4 ? 4 : D <= 8 ? 8 : D <= 16 ? 16 : 32; }
+inline size_t wide_pack_bytes(long M, int D) {
+  return ((size_t)M * (wide_dp(D) + 1) * sizeof(double) + 255) & ~(size_t)255;
+}
+// split tiles of the widest group of Bt right-hand sides: the full groups of PJ_MAX_R and the remainder plan differently
+size_t wide_part_bytes(const mgp_handle* h, long M, long Bt) {
+  size_t part_bytes = 0;
+  const long widths[2] = {Bt < PJ_MAX_R ? Bt : (long)PJ_MAX_R, Bt > PJ_MAX_R ? Bt % PJ_MAX_R : 0};
+  for (const long g : widths) {
+    if (g <= 0) continue;
+    const long RP = (g + 15) / 16 * 16, PB = g <= 128 ? 128 : 64;
+    for (long c0 = 0; c0 < M; c0 += PJ_CHUNK_B) {
+      const long tiles = ((M - c0 < PJ_CHUNK_B ? M - c0 : PJ_CHUNK_B) + PB - 1) / PB;
+      long ns, rw;
+      pj_plan(h, tiles, M, &ns, &rw);
+      const size_t bytes = (size_t)ns * tiles * PB * RP * sizeof(double);
+      if (bytes > part_bytes) part_bytes = bytes;
+    }
+  }
+  return (part_bytes + 255) & ~(size_t)255;
+}
+
+template <int KIND, int DP>
+int kmm_wide_dp(mgp_handle* h, const mgp_kernel* k, const double* Z, long M, const double* lam, const double* P,
+                long Bt, double* out, const int* gate) {
+  const SweepParams prm = mgp_make_params(k);
+  const int D = k->D;
+  const double* Xp = (const double*)h->prj;
+  double* part = (double*)((char*)h->prj + wide_pack_bytes(M, D));
+  for (long g0 = 0; g0 < Bt; g0 += PJ_MAX_R) {
+    const int r = (int)(Bt - g0 < PJ_MAX_R ? Bt - g0 : PJ_MAX_R), RP = (r + 15) / 16 * 16;
+    const int PB = r <= 128 ? 128 : 64;
+    const double* Pg = P + g0 * M;
+    double* og = out + g0 * M;
+    for (long c0 = 0; c0 < M; c0 += PJ_CHUNK_B) {
+      const long Bc = M - c0 < PJ_CHUNK_B ? M - c0 : PJ_CHUNK_B;
+      const long tiles = (Bc + PB - 1) / PB;
+      long ns, rw;
+      pj_plan(h, tiles, M, &ns, &rw);
+      const double* xs = Z + c0 * D;
+      dim3 grid((unsigned)tiles, 1, (unsigned)ns);
+#define MGP_PJ(MTV, NQV)                                                                                            \
+  hipLaunchKernelGGL((knm_project_kernel<DP, KIND, MTV, NQV, PjCgGate>), grid, dim3(256), 0, h->stream, xs, Bc, Xp, M, \
+                     Pg, 1L, M, r, part, rw, D, RP, prm, PjCgGate{gate})
+      if (r <= 32) MGP_PJ(4, 1);
+      else if (r <= 64) MGP_PJ(4, 2);
+      else if (r <= 128) MGP_PJ(4, 4);
+      else MGP_PJ(2, 8);
+#undef MGP_PJ
+      MGP_LAUNCH_CHECK(h);
+      hipLaunchKernelGGL(kmm_wide_finish_kernel, dim3((unsigned)((Bc + FT_I - 1) / FT_I), (unsigned)(RP / FT_B)),
+                         dim3(256), 0, h->stream, (const double*)part, (int)ns, tiles * PB, RP, Bc, r, k->variance,
+                         lam + c0, Pg + c0, og + c0, M, gate);
+      MGP_LAUNCH_CHECK(h);
+    }
+  }
+  return MGP_OK;
+}
+
 }  // namespace
+
+bool mgp_kmm_wide_serves(const mgp_kernel* k) { return k->dtype == MGP_F64 && k->D <= MGP_FUSED_MAX_D; }
+
+int mgp_kmm_wide_prepare(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, int64_t Bt, const int* gate) {
+  const size_t pack_bytes = wide_pack_bytes(M, k->D);
+  MGP_TRY(mgp_reserve(h, &h->prj, &h->prj_bytes, pack_bytes + wide_part_bytes(h, M, Bt)));
+  const SweepParams prm = mgp_make_params(k);
+  return mgp_with_dp(k->D, [&](auto dp) -> int {
+    hipLaunchKernelGGL((pj_pack_kernel<decltype(dp)::value, PjCgGate>), dim3((unsigned)((M + 255) / 256)), dim3(256), 0,
+                       h->stream, (const double*)Z, (long)M, k->D, prm, (double*)h->prj, PjCgGate{gate});
+    MGP_LAUNCH_CHECK(h);
+    return MGP_OK;
+  });
+}
+
+int mgp_kmm_wide_apply(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, const void* lambda, const void* P,
+                       int64_t Bt, void* out, const int* gate) {
+  if (h->wide_pack_src == Z && h->wide_pack_m == M) {  // inside a solve: packed before its loop, the arena sized there
+    if (wide_pack_bytes(M, k->D) + wide_part_bytes(h, M, Bt) > h->prj_bytes)
+      return mgp_fail(h, MGP_E_NOMEM, "many-column operator: %lld right-hand sides do not fit the arena reserved for the solve",
+                      (long long)Bt);
+  } else {
+    MGP_TRY(mgp_kmm_wide_prepare(h, k, Z, M, Bt, gate));
+  }
+  return mgp_with_kind(k->kind, [&](auto kind) {
+    return mgp_with_dp(k->D, [&](auto dp) {
+      return kmm_wide_dp<decltype(kind)::value, decltype(dp)::value>(h, k, (const double*)Z, M, (const double*)lambda,
+                                                                     (const double*)P, Bt, (double*)out, gate);
+    });
+  });
+}
 
 extern "C" int mgp_knm_project(mgp_handle* h, const mgp_kernel* k, const void* Xs, int64_t B, const void* X, int64_t N,
                                const void* R, int32_t r, int r_layout, void* proj, void* sqnorm) {

@@ -66,8 +66,21 @@ enum { MGP_PRE_EYE = 0, MGP_PRE_JACOBI = 1, MGP_PRE_BLOCK = 2, MGP_PRE_DENSE = 3
        MGP_PRE_LOWRANK = 5 };
 
 /* MGP_OP_KXX_NOISE: (k(X,X) + s2 I) applied matrix-free with each unordered pair evaluated once (mgp_kxx_matvec);
- * fields kernel, X, N, s2 and n == N; single rank: `allreduce` / `comm` set is MGP_E_BADARG */
-enum { MGP_OP_DENSE = 0, MGP_OP_SGPR = 1, MGP_OP_KMM_LAMBDA = 2, MGP_OP_KXX_NOISE = 3 };
+ * fields kernel, X, N, s2 and n == N; single rank: `allreduce` / `comm` set is MGP_E_BADARG
+ * MGP_OP_KMM_LAMBDA_WIDE: the many-column form of MGP_OP_KMM_LAMBDA -- the same fields (kernel, Z, M == n, lambda), the
+ * same checks, the same meaning out[Bt, M] = P[Bt, M] (k(Z, Z) + diag(lambda)), results equal to rounding.  The right-hand
+ * sides go in groups of at most 256 through the kernel of mgp_knm_project (Xs = X = Z, R = P as MGP_ROWS), so each
+ * kernel value is evaluated once per group on the vector ALU and contracted with the whole group on the fp64 matrix
+ * cores, where the sweep of MGP_OP_KMM_LAMBDA evaluates it once per 8 right-hand sides; a second kernel adds the split
+ * tiles in a fixed order, scales, adds lambda_i P[b, i] and writes out (no float atomics: two calls are bit-identical).
+ * It pays from some tens of right-hand sides on (DESIGN 4.15 has the table).  Fallbacks: fp32 or D > MGP_FUSED_MAX_D take
+ * exactly the code of MGP_OP_KMM_LAMBDA and give its bits.  mgp_pcg_solve / mgp_pcg_solve_record pack Z once, before the
+ * loop; mgp_operator_apply packs per call.  Scratch, the arena of mgp_knm_project ("prj"; MGP_E_NOMEM from a fixed pool
+ * that is too small): 8 M (D' + 1) rounded up to 256, plus 8 t r' (min(M', 2^16) / t + s) rounded up to 256 bytes for
+ * the widest group, r = min(Bt, 256) columns (and Bt mod 256 when Bt > 256), r' = r rounded up to 16, t = 128 for
+ * r <= 128 and 64 above, M' = M rounded up to t, D' = D rounded up to 2, 4, 8, 16 or 32, s <= 4 CUs + 1 the workgroups
+ * added by the split -- at most 8 M (D' + 1) + 512 r' (1024 + 4 CUs + 1) + 512 bytes. */
+enum { MGP_OP_DENSE = 0, MGP_OP_SGPR = 1, MGP_OP_KMM_LAMBDA = 2, MGP_OP_KXX_NOISE = 3, MGP_OP_KMM_LAMBDA_WIDE = 4 };
 
 typedef struct mgp_handle mgp_handle;
 /* one RCCL communicator rank (wraps ncclComm_t); see "collectives" below */
@@ -105,7 +118,7 @@ typedef struct {
   const void* Z; int64_t M;
   const void* Kmm;
   double s2;
-  /* MGP_OP_KMM_LAMBDA: (k(Z,Z) + diag(lambda)) applied matrix-free; lambda [M] device */
+  /* MGP_OP_KMM_LAMBDA, MGP_OP_KMM_LAMBDA_WIDE: (k(Z,Z) + diag(lambda)) applied matrix-free; lambda [M] device */
   const void* lambda;
   mgp_allreduce_fn allreduce; void* allreduce_ctx;
   /* MGP_OP_SGPR with the `allreduce` hook, optional: caller-owned device buffer of Bt_max*M + 1
