@@ -109,13 +109,22 @@ def kxx_grad(spec, X, U, V, layout=COLS):
 def kmn_knm_vjp(spec, X, Z, Gq, Y=None, Gb=None, need_dZ=False):
     """VJP of (theta, Z) -> (Q, B) = (K_mn K_nm, K_mn Y), K = k(X, Z), at the cotangents Gq [M, M] (need not be
     symmetric) and Gb [M, P]: (dvariance: float, [dl_d for d < D], dZ [M, D] or None).  Nothing N x M beyond one row
-    panel is formed (`mgp_kmn_knm_vjp`).  fp64 and D <= 32 only: libmgp refuses anything else (MgpError)."""
+    panel is formed (`mgp_kmn_knm_vjp`).  fp64 and D <= 32 only: libmgp refuses anything else (MgpError).
+
+    `Gq=None` means Gq = 0: the cotangent of K is then W = Y Gb^T alone, of rank P, nothing [M, M] is touched and Y and
+    Gb are required (ValueError without them).  X and Z may be the same tensor; with Y = [U | V] and Gb = [V | U] on
+    (Z, Z) the cotangent is U V^T + V U^T, so dZ is the whole gradient of sum_r u_r^T k(Z, Z) v_r in Z and dvariance,
+    dl are twice `kxx_grad(spec, Z, U, V)`."""
     X = _points(X, "X", spec.D)
     Z = _points(Z, "Z", spec.D, X.dtype)
     N, M = X.shape[0], Z.shape[0]
     if M < 1:
         raise ValueError("kmn_knm_vjp needs M >= 1")
-    Gq = _hip.check_tensor(Gq, "Gq", dtype=X.dtype, shape=(M, M))
+    if Gq is None:
+        if Y is None or Gb is None:
+            raise ValueError("Gq=None (a rank-P cotangent Y Gb^T) needs Y and Gb")
+    else:
+        Gq = _hip.check_tensor(Gq, "Gq", dtype=X.dtype, shape=(M, M))
     if (Y is None) != (Gb is None):
         raise ValueError("Y and Gb go together")
     P = 0
@@ -125,6 +134,8 @@ def kmn_knm_vjp(spec, X, Z, Gq, Y=None, Gb=None, need_dZ=False):
             raise ValueError(f"Y must be [N={N}, P], got {tuple(Y.shape)}")
         P = Y.shape[1]
         Gb = _hip.check_tensor(Gb, "Gb", dtype=X.dtype, shape=(M, P))
+    if Gq is None and P < 1:
+        raise ValueError("Gq=None needs P >= 1 columns in Y and Gb")
     dZ = torch.empty((M, spec.D), dtype=X.dtype, device=X.device) if need_dZ else None
     dvar = ctypes.c_double(0.0)
     dls = (ctypes.c_double * _hip.MGP_MAX_D)()

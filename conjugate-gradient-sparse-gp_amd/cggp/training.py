@@ -49,7 +49,8 @@ class Parameter:
 
 
 class _KBlock(torch.autograd.Function):
-    """K = k(A, B) (+ jitter I): forward `mgp_k_dense`, backward `mgp_k_dense_vjp`."""
+    """K = k(A, B) (+ jitter I): forward `mgp_k_dense`, backward `mgp_k_dense_vjp`; where A or B needs a gradient
+    (trainable inducing inputs) it comes from `k_grad_points`.  K(Z) passes Z twice and autograd adds the two."""
 
     @staticmethod
     def forward(ctx, variance, lengthscales, A, B, kind, jitter):
@@ -66,7 +67,10 @@ class _KBlock(torch.autograd.Function):
         gv = torch.tensor(dvar, dtype=torch.float64).reshape(ctx.v_shape)
         n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
         gl = torch.tensor(dls if n_l > 1 else [sum(dls)], dtype=torch.float64).reshape(ctx.l_shape)
-        return gv, gl, None, None, None, None
+        dA = dB = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dA, dB = k_grad_points(ctx.spec.kind, ctx.spec.variance, ctx.spec.lengthscales, A, B, G)
+        return (gv, gl, dA if ctx.needs_input_grad[2] else None, dB if ctx.needs_input_grad[3] else None, None, None)
 
 
 class TrainableKernel:
@@ -127,9 +131,24 @@ def _theta_grads(dvar, dls, v_shape, l_shape):
     return torch.tensor(dvar, dtype=torch.float64).reshape(v_shape), gl
 
 
+def _kzz_bilinear_grads(spec, Z, U, V, need_z):
+    """(dvariance, [dl_d], dZ or None) of sum_r u_r^T k(Z, Z) v_r for U, V [M, R], nothing [M, M] formed.  Without dZ:
+    `mgp_kxx_grad`, as ever.  With it: ONE `mgp_kmn_knm_vjp` call on (Z, Z) with Gq = NULL, Y = [U | V], Gb = [V | U],
+    whose cotangent U V^T + V U^T makes its dZ the whole derivative in Z (both arguments of k) and its dvariance, dl
+    twice the bilinear form's, halved here."""
+    if not need_z:
+        dvar, dls = ops.kxx_grad(spec, Z, U, V)
+        return dvar, dls, None
+    Zd = Z.detach()
+    Y, Gb = torch.cat([U, V], dim=1), torch.cat([V, U], dim=1)
+    dvar, dls, dZ = ops.kmn_knm_vjp(spec, Zd, Zd, None, Y, Gb, need_dZ=True)
+    return 0.5 * dvar, [0.5 * v for v in dls], dZ
+
+
 class _KzzTimes(torch.autograd.Function):
     """k(Z, Z) V for V [M, R], K never formed: forward `mgp_knm_matvec` on (Z, Z); backward dV = k(Z, Z) G and
-    (dvariance, dlengthscales) = sum_r g_r^T (dK/dtheta) v_r by `mgp_kxx_grad`."""
+    (dvariance, dlengthscales) = sum_r g_r^T (dK/dtheta) v_r by `mgp_kxx_grad`; when Z needs a gradient, all three of
+    (dvariance, dlengthscales, dZ) by `_kzz_bilinear_grads`."""
 
     @staticmethod
     def forward(ctx, variance, lengthscales, Z, V, kind):
@@ -143,16 +162,17 @@ class _KzzTimes(torch.autograd.Function):
     def backward(ctx, G):
         Z, V = ctx.saved_tensors
         G = G.contiguous()
-        gv, gl = _theta_grads(*ops.kxx_grad(ctx.spec, Z, G, V), ctx.v_shape, ctx.l_shape)
+        dvar, dls, dZ = _kzz_bilinear_grads(ctx.spec, Z, G, V, ctx.needs_input_grad[2])
+        gv, gl = _theta_grads(dvar, dls, ctx.v_shape, ctx.l_shape)
         dV = ops.knm_matvec(ctx.spec, Z, Z, G) if ctx.needs_input_grad[3] else None
-        return gv, gl, None, dV, None
+        return gv, gl, dZ, dV, None
 
 
 class _KzzLambdaSolve(torch.autograd.Function):
     """X = (k(Z, Z) + diag lam)^-1 rhs for rhs [M, R] by the device CG on `KmmLambdaOperator`.  Backward, with
     Gb = (k(Z, Z) + diag lam)^-1 G (`_adjoint_solve`: the shortcut and the warm start of `_CGFunction` where they
     apply): d rhs = Gb, (dvariance, dlengthscales) = -sum_r gb_r^T (dK/dtheta) x_r (`mgp_kxx_grad`),
-    dlam = -sum_r Gb o X."""
+    dlam = -sum_r Gb o X; when Z needs a gradient, dZ of the same form by `_kzz_bilinear_grads`."""
 
     @staticmethod
     def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg, wide=False):
@@ -172,16 +192,22 @@ class _KzzLambdaSolve(torch.autograd.Function):
         sol, rows, err = ctx.saved_tensors
         op = ctx.op
         Gb = _adjoint_solve(op, sol, rows, err, G.t().contiguous(), ctx.cfg, True).contiguous()
-        dvar, dls = ops.kxx_grad(op.spec, op.Z, Gb, sol, ops.ROWS)
+        dZ = None
+        if ctx.needs_input_grad[4]:
+            dvar, dls, dZ = _kzz_bilinear_grads(op.spec, op.Z, Gb.t(), sol.t(), True)
+            dZ = -dZ
+        else:
+            dvar, dls = ops.kxx_grad(op.spec, op.Z, Gb, sol, ops.ROWS)
         gv, gl = _theta_grads(-dvar, [-v for v in dls], ctx.v_shape, ctx.l_shape)
-        grads = (gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), None, None, None, None)
+        grads = (gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), dZ, None, None, None)
         return grads[:len(ctx.needs_input_grad)]  # `wide` is optional in apply()
 
 
 class _KzzLambdaLogdet(torch.autograd.Function):
     """`eval_logdet` on the operator: value 0.0; backward (dvariance, dlengthscales) = df sum_r s_r^T (dK/dtheta) z_r / P
     and dlam = df sum_r S o Zp / P, with S = (k(Z, Z) + diag lam)^-1 Zp handed in (the trace estimator's solve, reused)
-    or, when `solution` is None, solved in the backward pass as the reference does (`cggp/models.py:38-41`)."""
+    or, when `solution` is None, solved in the backward pass as the reference does (`cggp/models.py:38-41`); when Z
+    needs a gradient, dZ of the same form by `_kzz_bilinear_grads`."""
 
     @staticmethod
     def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg, wide=False):
@@ -203,9 +229,11 @@ class _KzzLambdaLogdet(torch.autograd.Function):
                 S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous(), wide=ctx.wide), probes)
         P = probes.shape[1]
         scale = float(df) / P
-        dvar, dls = ops.kxx_grad(kern.spec(Z.shape[1]), Z, S.contiguous(), probes.contiguous())
+        dvar, dls, dZ = _kzz_bilinear_grads(kern.spec(Z.shape[1]), Z, S.contiguous(), probes.contiguous(),
+                                            ctx.needs_input_grad[5])
         gv, gl = _theta_grads(scale * dvar, [scale * v for v in dls], ctx.v_shape, ctx.l_shape)
-        grads = (gv, gl, scale * (S * probes).sum(dim=1), None, None, None, None, None, None)
+        grads = (gv, gl, scale * (S * probes).sum(dim=1), None, None, None if dZ is None else scale * dZ, None, None,
+                 None)
         return grads[:len(ctx.needs_input_grad)]  # `wide` is optional in apply()
 
 
@@ -225,17 +253,31 @@ class TrainableCGGP:
     The exact trace (`num_probes=None` without `probes`) needs M right-hand sides and raises `ValueError`.
     `fused_solves=True` works there too: one operator solve on the columns [pseudo_u, K_mn, probes].
     `wide_solves` (False, True or "auto"; with `matrix_free=True` only) is handed to every `KmmLambdaOperator`, as in
-    `models.CGGP`."""
+    `models.CGGP`.
+
+    `trainable_inducing=True` (the reference's `--tip`: `set_trainable(model.inducing_variable, tip)`,
+    `paper_cli_geospatial.py:237`): the model keeps its own copy of Z as a leaf, `parameters()` ends with it and
+    `frozen_model()` hands over a detached copy.  The dense model differentiates its kernel blocks in Z by
+    `k_grad_points` (any D); with `matrix_free=True` each of the three nodes makes one `mgp_kmn_knm_vjp` call on (Z, Z)
+    with a rank-2R cotangent (fp64, D <= 32: `ValueError` at construction beyond).  `pseudo_u` and `cluster_counts`
+    stay frozen (`models.py:220`).  The reference's `--tip` flow passes `update_fn=None`; replacing `model.Z` from an
+    `update_fn` while it is trainable is not supported (the optimiser would keep stepping the old leaf)."""
 
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
                  num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
-                 wide_solves=False):
+                 wide_solves=False, trainable_inducing=False):
         from .conjugate_gradient import check_wide
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
         self.kernel = kernel if isinstance(kernel, TrainableKernel) else TrainableKernel(kernel)
         self.noise_p = Parameter(noise_variance)
+        self.trainable_inducing = bool(trainable_inducing)
+        if self.trainable_inducing:
+            if matrix_free and Z.shape[1] > 32:
+                raise ValueError(f"matrix_free=True with trainable_inducing=True needs D <= 32, got D={Z.shape[1]} "
+                                 "(the dense model takes any D)")
+            Z = Z.detach().clone().contiguous().requires_grad_(True)
         self.Z = Z
         self.pseudo_u = pseudo_u.reshape(-1, 1)
         self.cluster_counts = cluster_counts.reshape(-1, 1)
@@ -253,7 +295,8 @@ class TrainableCGGP:
         self.matrix_free = bool(matrix_free)
 
     def parameters(self):
-        return self.kernel.parameters() + [self.noise_p.raw]
+        ps = self.kernel.parameters() + [self.noise_p.raw]
+        return ps + [self.Z] if self.trainable_inducing else ps
 
     def _elbo_matrix_free(self, data, probes):
         x, y = data
@@ -356,7 +399,8 @@ class TrainableCGGP:
 
     def frozen_model(self):
         from .models import CGGP
-        return CGGP(self.kernel.frozen(), self.noise_p.value, self.Z, self.conjugate_gradient,
+        Z = self.Z.detach().clone() if self.trainable_inducing else self.Z
+        return CGGP(self.kernel.frozen(), self.noise_p.value, Z, self.conjugate_gradient,
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
                     num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves)
 
@@ -568,6 +612,25 @@ def kmm_grad_z(name, variance, lengthscales, Z, G, max_elems=1 << 24):
         fp = _profile_grad(name, (diff * diff).sum(dim=2))
         out[i0:i0 + step] = ((S[i0:i0 + step] * fp)[:, :, None] * diff).sum(dim=1)
     return out * (2.0 * float(variance) / ls)
+
+
+def k_grad_points(name, variance, lengthscales, A, B, G, max_elems=1 << 24):
+    """(dA [na, D], dB [nb, D]) through K = k(A, B) given a dense cotangent G = dL/dK [na, nb]:
+    dA_i = sum_j G_ij dk(a_i, b_j)/da_i and dB_j = sum_i G_ij dk(a_i, b_j)/db_j, direct differences, any D, rows of A in
+    chunks of at most `max_elems` temporaries.  For the dense blocks only (K_mn of a batch, K_mm of the dense model); at
+    A = B = Z, dA + dB is `kmm_grad_z(Z, G)`."""
+    ls = torch.as_tensor(lengthscales, dtype=A.dtype, device=A.device).reshape(-1)
+    As, Bs = A.detach() / ls, B.detach() / ls
+    (na, D), nb = As.shape, Bs.shape[0]
+    dA, dB = torch.empty_like(As), torch.zeros_like(Bs)
+    step = max(1, max_elems // max(1, nb * D))
+    for i0 in range(0, na, step):
+        diff = As[i0:i0 + step, None, :] - Bs[None, :, :]
+        w = (G[i0:i0 + step] * _profile_grad(name, (diff * diff).sum(dim=2)))[:, :, None] * diff
+        dA[i0:i0 + step] = w.sum(dim=1)
+        dB -= w.sum(dim=0)
+    scale = 2.0 * float(variance) / ls
+    return dA * scale, dB * scale
 
 
 class _SGPRElbo(torch.autograd.Function):

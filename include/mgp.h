@@ -287,7 +287,8 @@ int mgp_kxx_grad(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, c
  * through Q, K_mn y and y^T y); mgp_k_dense_vjp would need the [N, M] cotangent W = K (Gq + Gq^T) + Y Gb^T.  Returns
  *   dvariance = sum_nm W_nm dk_nm/dvariance,  dlengthscales[d] = sum_nm W_nm dk_nm/dl_d     (host doubles, ARD)
  *   dZ[m, d]  = sum_n  W_nm dk_nm/dz_md                                                     ([M, D] device, row-major)
- * Y [N, P] and Gb may be NULL with P = 0; dZ may be NULL (not computed).  Gq need not be symmetric: Gq + Gq^T is used.
+ * Y [N, P] and Gb may be NULL with P = 0; dZ may be NULL (not computed).  Gq need not be symmetric: Gq + Gq^T is used
+ * (Gq = NULL: see the last paragraph).
  * fp64 only (fp32: MGP_E_DTYPE), D <= MGP_FUSED_MAX_D (else MGP_E_BADARG), N >= 0, M >= 1, P >= 0; N = 0 writes zeros.
  * dk/dr2 as mgp_k_dense_vjp forms it, r2 from direct differences; Matern-1/2 adds 0 to the lengthscales and to dZ
  * below GPflow's r2 floor of 1e-36 (a data row equal to an inducing point gives no NaN).  Row panels of at most 256 MiB
@@ -298,7 +299,17 @@ int mgp_kxx_grad(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, c
  * too small): 16 R M + 8 M^2 + 8 (4 CUs + B) (D' + 1) + (dZ ? 8 M D' (4 CUs / B + 2) : 0) + 2048 bytes, R = the
  * panel rows (min(N, 2^25 / M) rounded down to 16, at least 16), B = ceil(M / 256), D' = D rounded up to 4, 8, 16
  * or 32 -- at most 512 MiB + 8 M^2 + O(CUs (M + 256) D'), nothing N x M beyond one row panel.  Synchronises the
- * stream. */
+ * stream.
+ * Gq = NULL means Gq = 0: the cotangent of K is W = Y Gb^T alone, of rank P, and P >= 1 with Y and Gb is required
+ * (MGP_E_BADARG otherwise).  Nothing [M, M] is read, written or reserved.  X and Z may be the same buffer (with
+ * Y = [U | V], Gb = [V | U] the call differentiates sum_r u_r^T k(Z, Z) v_r: dZ in both arguments of k, dvariance and
+ * dlengthscales twice mgp_kxx_grad's); coincident points and the diagonal pairs add 0 to dlengthscales and dZ, never a
+ * NaN.  Same arithmetic, determinism and shard additivity as above.  P <= 12 (MGP_KVJP_P_FUSED at build time): a
+ * fused pair kernel forms W_nm = sum_p Y_np Gb_mp on the fly in passes of at most C = 16 columns (8 for Matern-1/2)
+ * that add to the running sums in pass order; scratch 8 R' (D' + C) + 8 (4 CUs + B) (D' + 1) +
+ * (dZ ? 8 M D' (4 CUs / B + 2) : 0) + 1280 bytes, R' = min(N, 2^23 / (D' + C)) -- at most 64 MiB +
+ * O(CUs (M + 256) D').  Larger P: row panels of W by the NT GEMM and the pair kernel above; scratch 8 R M + the same
+ * partials, R as above -- at most 256 MiB + O(CUs (M + 256) D'). */
 int mgp_kmn_knm_vjp(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
                     const void* Gq, const void* Y, const void* Gb, int32_t P, double* dvariance, double* dlengthscales,
                     void* dZ);
