@@ -18,7 +18,7 @@ MGP_COMM_ID_BYTES = 128
 F32, F64 = 0, 1
 SE, MATERN12, MATERN32, MATERN52 = 0, 1, 2, 3
 COLS, ROWS = 0, 1
-PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK, PRE_LOWRANK = 0, 1, 2, 3, 4, 5
+PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK, PRE_LOWRANK, PRE_LOWRANK_WIDE = 0, 1, 2, 3, 4, 5, 6
 OP_DENSE, OP_SGPR, OP_KMM_LAMBDA, OP_KXX_NOISE, OP_KMM_LAMBDA_WIDE = 0, 1, 2, 3, 4
 
 KERNEL_KINDS = {"se": SE, "matern12": MATERN12, "matern32": MATERN32, "matern52": MATERN52}

@@ -9,7 +9,8 @@ Same names, argument order and shapes as the reference:
   max_steps_cycle=None)`; `__call__(matrix[n,n], rhs[n,Bt], initial_solution=None) -> [n,Bt]`
   (reference :160-212)
 * `CGPreconditioner / EyePreconditioner / BlockPreconditioner`     (reference :125-157)
-* `PivotedCholeskyPreconditioner(rank, rel_tol)`: build-side addition for `KxxNoiseOperator` (exact GPR)
+* `PivotedCholeskyPreconditioner(rank, rel_tol, wide)`: build-side addition for `KxxNoiseOperator` (exact GPR) and
+  `KmmLambdaOperator` (matrix-free CDGP)
 
 The loop itself (`cg_step`, the stopping rule, the breakdown guards, the residual refresh)
 runs in libmgp (`csrc/cg.hip`); this module only validates, lays tensors out and wires the
@@ -532,22 +533,51 @@ class SubsampledNormalPreconditioner(DensePreconditioner):
         super().__init__((0.5 * (Pinv + Pinv.t())).to(operator.dtype).contiguous())
 
 
+# `wide="auto"` of `PivotedCholeskyPreconditioner` takes the many-column application (`MGP_PRE_LOWRANK_WIDE`) from this
+# many right-hand sides on.  The rule, fixed before measuring: the smallest measured width such that at every measured
+# point with at least that many columns (rank 128; 16, 24, 32, 48, 64, 128, 256 columns; n = 2^12, 2^14, 2^16, 2^17) a
+# CG start-up with the many-column form took at most 0.9 of the same start-up with the 16-column form.  It held at all
+# 28 points, from 0.82 (16 columns, n = 2^12) down to 0.10 (256 columns), so the rule gives the smallest width measured;
+# below it nothing was measured and "auto" keeps the 16-column form (tools/run_cdgp_precond.py,
+# profiles/cdgp_precond_times.json).  None would mean that no width qualified.
+LOWRANK_WIDE_MIN_COLUMNS = 16
+
+
+def lowrank_wide_auto(dtype, columns):
+    """The rule behind `PivotedCholeskyPreconditioner(wide="auto")`: fp64 and at least LOWRANK_WIDE_MIN_COLUMNS columns."""
+    return (dtype == torch.float64 and LOWRANK_WIDE_MIN_COLUMNS is not None
+            and int(columns) >= LOWRANK_WIDE_MIN_COLUMNS)
+
+
 class PivotedCholeskyPreconditioner(CGPreconditioner):
     """P = L^T L + D with L [k, N] the rank-k partial pivoted Cholesky factor of K = k(X, X) and D = s2 I: the
     standard preconditioner of the exact-GP system K + s2 I (Harbrecht et al. 2012; Gardner et al. 2018).  Build-side
     addition, opt-in: `ConjugateGradient(thr, preconditioner=PivotedCholeskyPreconditioner())`.
 
+    For matrix-free CDGP (`KmmLambdaOperator`, either form: `CGGP(..., matrix_free=True)`,
+    `TrainableCGGP(..., matrix_free=True)`) the same with K = k(Z, Z) and D = diag(lambda), lambda = s2 / cluster size.
+    L depends on (Z, kernel, rank, rel_tol) only and is kept while those stay; the Woodbury part (B, D^-1, log|P|) is
+    re-formed when the values of lambda change (compared by value: the models make a new lambda tensor per call).  The
+    factor is a constant of a solve: it is built from detached values and no gradient flows through it.
+
+    `wide` (False, True or "auto") picks, per solve, the kernels that apply P^-1 inside the device CG loop: False
+    libmgp's `MGP_PRE_LOWRANK` (16 right-hand sides per group of launches), True its many-column form
+    `MGP_PRE_LOWRANK_WIDE` (256 per group, both products on the fp64 matrix cores), "auto" the many-column form from
+    `LOWRANK_WIDE_MIN_COLUMNS` right-hand sides on.  fp32 solves and recording solves (`ops.pcg_solve_record`) take
+    `MGP_PRE_LOWRANK` whatever `wide` says; `solve()` is `mgp_lowrank_apply` always.
+
     P^-1 = D^-1 - B^T B with B = C^-1 L D^-1 and C C^T = I_k + L D^-1 L^T (Woodbury), O(N k) per application;
     log|P| = 2 sum log C_ii + sum log D in closed form; z = L^T g1 + sqrt(D) g2 is a draw from N(0, P).
 
     Inside the device CG loop it is libmgp's `MGP_PRE_LOWRANK` kind.  The factor (`mgp_kxx_pivchol`, matrix-free) is
-    built for a `KxxNoiseOperator` on first use, cached, and rebuilt when the operator's kernel parameters, noise or
-    `X` change; any other operator is a `TypeError`.  `rank_` holds the rank reached (`rel_tol` may stop the factor
-    early).  It pays where K has a low-rank part -- low-dimensional inputs, smooth kernels -- and does nothing for
+    built for a `KxxNoiseOperator` or a `KmmLambdaOperator` on first use, cached, and rebuilt when the operator's kernel
+    parameters, noise or points change; any other operator is a `TypeError`.  `rank_` holds the rank reached
+    (`rel_tol` may stop the factor early).  It pays where K has a low-rank part -- low-dimensional inputs, smooth kernels -- and does nothing for
     high-dimensional inputs with short lengthscales.  `set_factor(L, D)` installs a hand-made factor
     (any device, also the CPU: `__call__`, `log_det` and `sample` are plain torch)."""
 
-    def __init__(self, rank=128, rel_tol=1e-10):
+    def __init__(self, rank=128, rel_tol=1e-10, wide=False):
+        self.wide = check_wide(wide)
         self.rank = int(rank)
         if not 1 <= self.rank <= 1024:
             raise ValueError("rank must be in [1, 1024]")
@@ -559,6 +589,7 @@ class PivotedCholeskyPreconditioner(CGPreconditioner):
         self._log_det = None
         self._key = self._key_ref = None
         self._normals = None
+        self._kmm_key = self._kmm_L = self._kmm_lam = None  # KmmLambdaOperator: the key of L, L, the lambda B was formed with
 
     def set_factor(self, L, D):
         """P = diag(D) + L^T L from a given L [k, n] and positive D (a number or [n])."""
@@ -583,16 +614,21 @@ class PivotedCholeskyPreconditioner(CGPreconditioner):
         return self
 
     def _prepare(self, op):
-        """Build (or reuse) the factor of a `KxxNoiseOperator`; a factor given through `set_factor` stays."""
+        """Build (or reuse) the factor of a `KxxNoiseOperator` or a `KmmLambdaOperator`; a factor given through
+        `set_factor` stays."""
         if self.L is not None and self._key is None:
             if self.L.shape[1] != op.shape[0]:
                 raise ValueError(f"the factor has n={self.L.shape[1]}, the operator n={op.shape[0]}")
             return
-        if not isinstance(op, KxxNoiseOperator):
+        if not isinstance(op, (KxxNoiseOperator, KmmLambdaOperator)):
             raise TypeError("PivotedCholeskyPreconditioner builds its factor for a KxxNoiseOperator (K + s2 I of exact "
-                            f"GP regression) only, got {type(op).__name__}; use set_factor(L, D) for another matrix")
+                            "GP regression) or a KmmLambdaOperator (K_mm + Lambda of matrix-free CDGP) only, got "
+                            f"{type(op).__name__}; use CGGP(..., matrix_free=True) for CDGP, or set_factor(L, D) for "
+                            "another matrix")
         if op.dtype != torch.float64:
             raise TypeError("PivotedCholeskyPreconditioner needs an fp64 operator (the factor is fp64 only)")
+        if isinstance(op, KmmLambdaOperator):
+            return self._prepare_kmm(op)
         if not op.noise_variance > 0.0:
             raise ValueError("PivotedCholeskyPreconditioner needs noise_variance > 0")
         X = op.X
@@ -604,6 +640,36 @@ class PivotedCholeskyPreconditioner(CGPreconditioner):
         self.set_factor(L, op.noise_variance)
         self.piv = piv
         self._key, self._key_ref = key, X  # the reference keeps id(X) from being reused
+
+    def _prepare_kmm(self, op):
+        """K = k(Z, Z), D = diag(lambda): L on the key of the exact-GP path with Z for X, B on the values of lambda."""
+        lam = op.lam.detach()
+        if not bool((lam > 0).all()):
+            raise ValueError("PivotedCholeskyPreconditioner needs lambda > 0 everywhere")
+        Z = op.Z
+        key = (id(Z), Z._version, tuple(Z.shape), op.spec.kind, op.spec.variance, tuple(op.spec.lengthscales),
+               self.rank, self.rel_tol)
+        fresh = key != self._kmm_key
+        if fresh:
+            L, piv, _ = ops.kxx_pivchol(op.spec, Z.detach(), self.rank, self.rel_tol)
+            self._kmm_key, self._kmm_L, self.piv = key, L, piv
+            self._key_ref = Z  # keeps id(Z) from being reused
+        if fresh or self._kmm_lam is None or self._key != ("kmm", key) or not torch.equal(lam, self._kmm_lam):
+            self.set_factor(self._kmm_L, lam)
+            self._kmm_lam = lam.clone()
+            self._key = ("kmm", key)  # not a hand-made factor: the next operator is looked at again
+
+    def _wide_for(self, dtype, columns):
+        wide = self.wide
+        if wide == "auto":
+            wide = lowrank_wide_auto(dtype, columns)
+        return bool(wide) and dtype == torch.float64
+
+    def _native_for(self, op, Bt):
+        st, keep = self._native(op)
+        if st.kind == _hip.PRE_LOWRANK and self._wide_for(op.dtype, Bt):
+            st.kind = _hip.PRE_LOWRANK_WIDE
+        return st, keep
 
     def _native(self, op):
         self._prepare(op)
@@ -622,7 +688,8 @@ class PivotedCholeskyPreconditioner(CGPreconditioner):
 
     def _require(self):
         if self.B is None:
-            raise RuntimeError("no factor yet: solve with a KxxNoiseOperator first, or call set_factor(L, D)")
+            raise RuntimeError("no factor yet: solve with a KxxNoiseOperator or a KmmLambdaOperator first, or call "
+                               "set_factor(L, D)")
 
     def solve(self, vec):
         """P^-1 applied to the rows of vec [Bt, n]: `mgp_lowrank_apply` on the GPU, torch elsewhere."""
@@ -632,7 +699,7 @@ class PivotedCholeskyPreconditioner(CGPreconditioner):
         return vec * self.diag_inv[None, :] - (vec @ self.B.t()) @ self.B
 
     def __call__(self, vec, mat):
-        if self.B is None or (self._key is not None and isinstance(mat, KxxNoiseOperator)):
+        if self.B is None or (self._key is not None and isinstance(mat, (KxxNoiseOperator, KmmLambdaOperator))):
             self._prepare(as_operator(mat))
         z = vec * self.diag_inv[None, :] - (vec @ self.B.t()) @ self.B
         return z, (z * vec).sum(dim=-1, keepdim=True)

@@ -1048,9 +1048,10 @@ def create_gpr_model(train_data, _kernel_fn, **model_kwargs):
     return GPR(train_data, kernel_fn(dim), noise_variance=0.1, **model_kwargs)
 
 
-def cdgp_class(kernel, likelihood, iv, error_threshold=1e-6, **kwargs):
-    """`cggp/cli_utils.py:439-441`."""
-    conjugate_gradient = ConjugateGradient(error_threshold)
+def cdgp_class(kernel, likelihood, iv, error_threshold=1e-6, preconditioner=None, **kwargs):
+    """`cggp/cli_utils.py:439-441`.  `preconditioner` (build-side addition): the `CGPreconditioner` of every solve, e.g.
+    `PivotedCholeskyPreconditioner()` with `matrix_free=True`."""
+    conjugate_gradient = ConjugateGradient(error_threshold, preconditioner=preconditioner)
     return CGGP(kernel, likelihood, iv, conjugate_gradient, **kwargs)
 
 

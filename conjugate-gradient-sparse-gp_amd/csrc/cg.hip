@@ -564,6 +564,7 @@ struct CgPrecond {
   const void* dense_inv = nullptr;       // MGP_PRE_DENSE: z = r @ Pinv through the symmetric product kernels
   const mgp_precond* cb = nullptr;       // MGP_PRE_CALLBACK: z produced by the caller's function, same step structure
   const mgp_precond* lowrank = nullptr;  // MGP_PRE_LOWRANK: z = diag_inv o r - (r B^T) B (pivchol.hip)
+  bool lowrank_wide = false;             // MGP_PRE_LOWRANK_WIDE: the same z by the many-column kernels
   bool dense_pre = false, need_z = false;  // z comes from outside the update kernels; z lives in the arena
 };
 
@@ -587,10 +588,11 @@ int decode_precond(mgp_handle* h, const mgp_precond* pre, CgPrecond& c) {
       if (!pre->apply || !pre->cb_r || !pre->cb_z)
         return mgp_fail(h, MGP_E_BADARG, "callback preconditioner needs apply, cb_r and cb_z");
       c.cb = pre;
-    } else if (pre->kind == MGP_PRE_LOWRANK) {
+    } else if (pre->kind == MGP_PRE_LOWRANK || pre->kind == MGP_PRE_LOWRANK_WIDE) {
       if (!pre->diag_inv || !pre->dense_inv || pre->num_blocks < 1)
         return mgp_fail(h, MGP_E_BADARG, "low-rank preconditioner needs diag_inv, B (dense_inv) and k (num_blocks) >= 1");
       c.lowrank = pre;
+      c.lowrank_wide = pre->kind == MGP_PRE_LOWRANK_WIDE;
     } else if (pre->kind != MGP_PRE_EYE) {
       return mgp_fail(h, MGP_E_BADARG, "unknown preconditioner kind %d", pre->kind);
     }
@@ -675,8 +677,8 @@ struct CgSolve {
       return MGP_OK;
     }
     if (pre.lowrank)
-      return mgp_lowrank_apply_gated(h, op->dtype, pre.lowrank->diag_inv, pre.lowrank->dense_inv,
-                                     pre.lowrank->num_blocks, n, a.r, Bt, z, gate);
+      return (pre.lowrank_wide ? mgp_lowrank_wide_apply_gated : mgp_lowrank_apply_gated)(
+          h, op->dtype, pre.lowrank->diag_inv, pre.lowrank->dense_inv, pre.lowrank->num_blocks, n, a.r, Bt, z, gate);
     return mgp_symm_matmul_gated(h, op->dtype, pre.dense_inv, n, a.r, Bt, z, gate);
   }
 

@@ -452,6 +452,10 @@ int mgp_symm_matmul_gated(mgp_handle* h, int dtype, const void* A, int64_t n, co
 // pivchol.hip: Z[Bt, n] = diag_inv o R - (R B^T) B, B [k, n]; gate: device int, skip if 0
 int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
                             const void* R, int64_t Bt, void* Z, const int* gate);
+// the many-column form (MGP_PRE_LOWRANK_WIDE): groups of at most 256 rows of R, both products on the fp64 matrix cores;
+// fp32 takes the code above
+int mgp_lowrank_wide_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
+                                 const void* R, int64_t Bt, void* Z, const int* gate);
 
 // Host tail of a kernel-block VJP.  part [nblocks][width] on the device holds per-workgroup sums: width - 1
 // lengthscale sums (the first k->D count), then the variance sum.  They are copied to the host and added in block

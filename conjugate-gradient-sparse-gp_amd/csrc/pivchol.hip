@@ -12,6 +12,10 @@
 // mgp_lowrank_apply: z = dinv o r - (r B^T) B for row batches, B [k, n].  Pass 1 is a reduction over n in two
 // stages (column-chunk partials, then their sum in chunk order; no float atomics), pass 2 forms z.  Both stream B
 // once; they are bandwidth-bound.  The gated form is the MGP_PRE_LOWRANK step of the device CG loop (cg.hip).
+//
+// MGP_PRE_LOWRANK_WIDE: the same z for batches of many rows, in groups of 256 instead of 16: both products as tiles
+// of v_mfma_f64_16x16x4_f64, pass 1 split over n with the per-split tiles added in split order (the sum kernel above),
+// pass 2 with the diagonal term fused into its store.  Three launches per 256 rows; no float atomics.
 #include "mgp_common.h"
 
 namespace {
@@ -301,7 +305,254 @@ int lowrank_apply_t(mgp_handle* h, const T* dinv, const T* B, long k, long n, co
   return MGP_OK;
 }
 
+// ---- the same z for many rows of R (MGP_PRE_LOWRANK_WIDE): both products on the fp64 matrix cores ------------------
+// A workgroup of four waves (2 x 2) owns LW_TB = 32 MT rows of the batch and LW_TN = 64 columns of the product, MT x 2
+// accumulator tiles of 16 x 16 per wave, and walks its contraction range in steps of 16 staged through LDS; the next
+// step's panels are fetched into registers before the current step's arithmetic (the scheme of project.hip).  Operand
+// and accumulator lanes of v_mfma_f64_16x16x4_f64 as in project.hip: A[row = lane & 15][k = lane >> 4],
+// B[k = lane >> 4][col = lane & 15], C[row = (lane >> 4) + 4 g][col = lane & 15].
+using LwAcc4 = __attribute__((ext_vector_type(4))) double;
+constexpr int LW_KC = 16;           // contraction elements per step
+constexpr int LW_STR = LW_KC + 2;   // LDS row stride of a panel held contraction-fastest
+constexpr int LW_TN = 64;           // columns of the product per workgroup
+constexpr int LW_RS = LW_TN + 16;   // LDS row stride of pass 2's panel of B: the four rows of an operand read fall in different banks
+constexpr int LW_GROUP = 256;       // rows of the batch per group of launches
+constexpr long LW_MIN_SPLIT = 256;  // columns of n a split of pass 1 holds at least
+
+// pass 1: part[split][b][i] = sum over the split's columns j of R[b, j] B[i, j], for b < BP and i < KP (the padded
+// extents: rows past bt and past k are staged as zeros and written as zeros)
+template <int MT>
+__global__ __launch_bounds__(256) void lowrank_wide_dot_kernel(const int* __restrict__ gate, const double* __restrict__ B,
+                                                               long k, long n, const double* __restrict__ R, int bt,
+                                                               long split_cols, double* __restrict__ part, long BP,
+                                                               long KP) {
+  if (gate != nullptr && *gate == 0) return;
+  constexpr int TB = 32 * MT;
+  constexpr int RL = TB * LW_KC / 256, BL = LW_TN * LW_KC / 256;
+  __shared__ double Rs[TB * LW_STR];     // [b][j]
+  __shared__ double Bs[LW_TN * LW_STR];  // [i][j]
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const long b0 = (long)blockIdx.x * TB, i0 = (long)blockIdx.y * LW_TN;
+  const long j_begin = (long)blockIdx.z * split_cols;
+  const long j_end = j_begin + split_cols < n ? j_begin + split_cols : n;
+  LwAcc4 acc[MT][2];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) acc[m][q] = LwAcc4{0, 0, 0, 0};
+  double rg[RL], bg[BL];
+  // 16 consecutive threads read the 16 columns of one row; what lies past the batch, past k or past the split is zero
+  auto fetch = [&](long j0) {
+    const int jj = t & (LW_KC - 1);
+    const long j = j0 + jj;
+#pragma unroll
+    for (int u = 0; u < RL; ++u) {
+      const long b = b0 + (t >> 4) + 16 * u;
+      rg[u] = (b < bt && j < j_end) ? R[b * n + j] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < BL; ++u) {
+      const long i = i0 + (t >> 4) + 16 * u;
+      bg[u] = (i < k && j < j_end) ? B[i * n + j] : 0.0;
+    }
+  };
+  auto stage = [&]() {
+    const int jj = t & (LW_KC - 1);
+#pragma unroll
+    for (int u = 0; u < RL; ++u) Rs[((t >> 4) + 16 * u) * LW_STR + jj] = rg[u];
+#pragma unroll
+    for (int u = 0; u < BL; ++u) Bs[((t >> 4) + 16 * u) * LW_STR + jj] = bg[u];
+  };
+  fetch(j_begin);
+  stage();
+  __syncthreads();
+  for (long j0 = j_begin; j0 < j_end; j0 += LW_KC) {
+    const bool more = j0 + LW_KC < j_end;
+    if (more) fetch(j0 + LW_KC);
+#pragma unroll
+    for (int ks = 0; ks < LW_KC; ks += 4) {
+      double af[MT], bf[2];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) af[m] = Rs[(wm * 16 * MT + m * 16 + (lane & 15)) * LW_STR + ks + (lane >> 4)];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) bf[q] = Bs[((2 * q + wn) * 16 + (lane & 15)) * LW_STR + ks + (lane >> 4)];
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) acc[m][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[m], bf[q], acc[m][q], 0, 0, 0);
+    }
+    __syncthreads();  // every wave has read the panels before they are overwritten
+    if (more) stage();
+    __syncthreads();
+  }
+  double* __restrict__ o = part + (long)blockIdx.z * BP * KP;
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const long i = i0 + (2 * q + wn) * 16 + (lane & 15);
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const long b = b0 + wm * 16 * MT + m * 16 + (lane >> 4) + 4 * g;
+        o[b * KP + i] = acc[m][q][g];  // b < BP and i < KP: the grid covers exactly the padded extents
+      }
+    }
+}
+
+// pass 2: Z[b, j] = dinv[j] R[b, j] - sum_i tt[b, i] B[i, j]; tt [BP, KP] holds zeros past bt and past k.  The
+// coefficients are staged 16 at a time, so any k fits
+template <int MT>
+__global__ __launch_bounds__(256) void lowrank_wide_form_kernel(const int* __restrict__ gate,
+                                                                const double* __restrict__ dinv,
+                                                                const double* __restrict__ B, long k, long n,
+                                                                const double* __restrict__ R, int bt,
+                                                                const double* __restrict__ tt, long KP,
+                                                                double* __restrict__ Z) {
+  if (gate != nullptr && *gate == 0) return;
+  constexpr int TB = 32 * MT;
+  constexpr int TL = TB * LW_KC / 256, BL = LW_KC * LW_TN / 256;
+  __shared__ double Ts[TB * LW_STR];     // [b][i]
+  __shared__ double Bs[LW_KC * LW_RS];   // [i][j]
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const long j0 = (long)blockIdx.x * LW_TN, b0 = (long)blockIdx.y * TB;
+  LwAcc4 acc[MT][2];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) acc[m][q] = LwAcc4{0, 0, 0, 0};
+  double tg[TL], bg[BL];
+  auto fetch = [&](long i0) {
+    // i0 + 15 < KP and b0 + TB <= BP: the padded tt needs no test
+#pragma unroll
+    for (int u = 0; u < TL; ++u) tg[u] = tt[(b0 + (t >> 4) + 16 * u) * KP + i0 + (t & (LW_KC - 1))];
+    const long j = j0 + (t & (LW_TN - 1));
+#pragma unroll
+    for (int u = 0; u < BL; ++u) {
+      const long i = i0 + (t >> 6) + 4 * u;
+      bg[u] = (i < k && j < n) ? B[i * n + j] : 0.0;
+    }
+  };
+  auto stage = [&]() {
+#pragma unroll
+    for (int u = 0; u < TL; ++u) Ts[((t >> 4) + 16 * u) * LW_STR + (t & (LW_KC - 1))] = tg[u];
+#pragma unroll
+    for (int u = 0; u < BL; ++u) Bs[((t >> 6) + 4 * u) * LW_RS + (t & (LW_TN - 1))] = bg[u];
+  };
+  fetch(0);
+  stage();
+  __syncthreads();
+  for (long i0 = 0; i0 < k; i0 += LW_KC) {
+    const bool more = i0 + LW_KC < k;
+    if (more) fetch(i0 + LW_KC);
+#pragma unroll
+    for (int ks = 0; ks < LW_KC; ks += 4) {
+      double af[MT], bf[2];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) af[m] = Ts[(wm * 16 * MT + m * 16 + (lane & 15)) * LW_STR + ks + (lane >> 4)];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) bf[q] = Bs[(ks + (lane >> 4)) * LW_RS + (2 * q + wn) * 16 + (lane & 15)];
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) acc[m][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[m], bf[q], acc[m][q], 0, 0, 0);
+    }
+    __syncthreads();
+    if (more) stage();
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const long j = j0 + (2 * q + wn) * 16 + (lane & 15);
+    if (j >= n) continue;
+    const double dv = dinv[j];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const long b = b0 + wm * 16 * MT + m * 16 + (lane >> 4) + 4 * g;
+        if (b < bt) Z[b * n + j] = mgp_fma(dv, R[b * n + j], -acc[m][q][g]);
+      }
+  }
+}
+
+// One group of bt <= LW_GROUP rows: the row tile, the padded extents, the split of n and the bytes of its scratch
+// (part [ns][BP][KP], then tt [BP][KP]).  About four workgroups per CU, at least LW_MIN_SPLIT columns per split: the
+// partials stay under 8 (4 CUs + tiles) LW_TB LW_TN bytes whatever n
+struct LwPlan {
+  int mt;
+  long BP, KP, ns, split_cols;
+  size_t bytes;
+};
+LwPlan lw_plan(const mgp_handle* h, long bt, long k, long n) {
+  LwPlan p;
+  p.mt = bt <= 32 ? 1 : bt <= 64 ? 2 : 4;
+  const long TB = 32L * p.mt;
+  p.BP = (bt + TB - 1) / TB * TB;
+  p.KP = (k + LW_TN - 1) / LW_TN * LW_TN;
+  const long tiles = (p.BP / TB) * (p.KP / LW_TN);
+  long ns = (4L * h->num_cus + tiles - 1) / tiles;
+  const long max_split = (n + LW_MIN_SPLIT - 1) / LW_MIN_SPLIT;
+  if (ns > max_split) ns = max_split;
+  if (ns < 1) ns = 1;
+  long cols = (n + ns - 1) / ns;
+  cols = (cols + LW_KC - 1) / LW_KC * LW_KC;
+  p.split_cols = cols;
+  p.ns = (n + cols - 1) / cols;
+  p.bytes = (size_t)(p.ns + 1) * p.BP * p.KP * sizeof(double);
+  return p;
+}
+
+int lowrank_wide_apply(mgp_handle* h, const double* dinv, const double* B, long k, long n, const double* R, long Bt,
+                       double* Z, const int* gate) {
+  // the arena for the widest group: the full groups and the remainder plan differently
+  size_t need = 0;
+  const long widths[2] = {Bt < LW_GROUP ? Bt : (long)LW_GROUP, Bt > LW_GROUP ? Bt % LW_GROUP : 0};
+  for (const long g : widths)
+    if (g > 0) {
+      const size_t b = lw_plan(h, g, k, n).bytes;
+      if (b > need) need = b;
+    }
+  MGP_TRY(mgp_reserve(h, &h->pch, &h->pch_bytes, need));
+  for (long g0 = 0; g0 < Bt; g0 += LW_GROUP) {
+    const int bt = (int)(Bt - g0 < LW_GROUP ? Bt - g0 : LW_GROUP);
+    const LwPlan p = lw_plan(h, bt, k, n);
+    const long total = p.BP * p.KP, TB = 32L * p.mt;
+    double* part = (double*)h->pch;
+    double* tt = part + p.ns * total;
+    const double* Rg = R + g0 * n;
+    double* Zg = Z + g0 * n;
+    const dim3 g1((unsigned)(p.BP / TB), (unsigned)(p.KP / LW_TN), (unsigned)p.ns);
+    const dim3 g2((unsigned)((n + LW_TN - 1) / LW_TN), (unsigned)(p.BP / TB));
+#define MGP_LW(MTV)                                                                                                   \
+  do {                                                                                                                \
+    hipLaunchKernelGGL((lowrank_wide_dot_kernel<MTV>), g1, dim3(256), 0, h->stream, gate, B, k, n, Rg, bt,            \
+                       p.split_cols, part, p.BP, p.KP);                                                               \
+    MGP_LAUNCH_CHECK(h);                                                                                              \
+    hipLaunchKernelGGL((lowrank_sum_kernel<double>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream,  \
+                       gate, (const double*)part, p.ns, total, tt);                                                   \
+    MGP_LAUNCH_CHECK(h);                                                                                              \
+    hipLaunchKernelGGL((lowrank_wide_form_kernel<MTV>), g2, dim3(256), 0, h->stream, gate, dinv, B, k, n, Rg, bt,     \
+                       (const double*)tt, p.KP, Zg);                                                                  \
+    MGP_LAUNCH_CHECK(h);                                                                                              \
+  } while (0)
+    if (p.mt == 1) MGP_LW(1);
+    else if (p.mt == 2) MGP_LW(2);
+    else MGP_LW(4);
+#undef MGP_LW
+  }
+  return MGP_OK;
+}
+
 }  // namespace
+
+// internal: the many-column form (MGP_PRE_LOWRANK_WIDE); fp32 takes the code of MGP_PRE_LOWRANK
+int mgp_lowrank_wide_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
+                                 const void* R, int64_t Bt, void* Z, const int* gate) {
+  if (dtype != MGP_F64) return mgp_lowrank_apply_gated(h, dtype, diag_inv, B, k, n, R, Bt, Z, gate);
+  return lowrank_wide_apply(h, (const double*)diag_inv, (const double*)B, k, n, (const double*)R, Bt, (double*)Z, gate);
+}
 
 // internal: the gated form the CG loop enqueues (steps past convergence do nothing)
 int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,

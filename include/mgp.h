@@ -61,9 +61,21 @@ enum { MGP_COLS = 0, MGP_ROWS = 1 };
 /* MGP_PRE_LOWRANK: diagonal plus low rank, z = diag_inv o r - (r B^T) B for each row of the batch, applied inside the
  * device CG loop (mgp_lowrank_apply's kernels, gated).  It reuses three fields of mgp_precond: diag_inv = D^-1 [n],
  * dense_inv = B [k, n] row-major, num_blocks = k >= 1.  For P = D + L^T L (L [k, n], e.g. mgp_kxx_pivchol's factor and
- * D = s2 I) pass B = C^-1 L D^-1 with C C^T = I_k + L D^-1 L^T (Woodbury); P^-1 must be positive definite. */
+ * D = s2 I) pass B = C^-1 L D^-1 with C C^T = I_k + L D^-1 L^T (Woodbury); P^-1 must be positive definite.
+ * MGP_PRE_LOWRANK_WIDE: the many-column form of MGP_PRE_LOWRANK -- the same fields, the same checks, the same meaning,
+ * the same place in the loop of mgp_pcg_solve, results equal to rounding; mgp_pcg_solve_record does not take it
+ * (MGP_E_BADARG).  Only the kernels that form z differ: the right-hand sides go in groups of at most 256 and both
+ * products run on the fp64 matrix cores -- T [b, k] = R B^T with n split over the workgroups and the per-split tiles
+ * added in split order by a second kernel, then Z = diag_inv o R - T B with the diagonal term fused into the store, so
+ * a step is three launches per 256 right-hand sides where MGP_PRE_LOWRANK makes three per 16.  No float atomics: two
+ * calls are bit-identical.  Any k in 1 .. 1024 and any n >= 1.  fp32 takes exactly the code of MGP_PRE_LOWRANK and
+ * gives its bits.  Scratch, the arena of mgp_kxx_pivchol ("pch"; counted by mgp_workspace_bytes; MGP_E_NOMEM from a
+ * fixed pool that is too small): 8 (s + 1) b' k' bytes for the widest group, b = min(Bt, 256) right-hand sides,
+ * b' = b rounded up to the row tile t (t = 32 for b <= 32, 64 for b <= 64, else 128), k' = k rounded up to 64 and
+ * s = min(ceil(4 CUs / ((b' / t) (k' / 64))), ceil(n / 256)) the splits of n (each a multiple of 16 columns) -- at
+ * most 8 (4 CUs + 64) 128 64 bytes (256 CUs: 68 MiB), whatever n. */
 enum { MGP_PRE_EYE = 0, MGP_PRE_JACOBI = 1, MGP_PRE_BLOCK = 2, MGP_PRE_DENSE = 3, MGP_PRE_CALLBACK = 4,
-       MGP_PRE_LOWRANK = 5 };
+       MGP_PRE_LOWRANK = 5, MGP_PRE_LOWRANK_WIDE = 6 };
 
 /* MGP_OP_KXX_NOISE: (k(X,X) + s2 I) applied matrix-free with each unordered pair evaluated once (mgp_kxx_matvec);
  * fields kernel, X, N, s2 and n == N; single rank: `allreduce` / `comm` set is MGP_E_BADARG
