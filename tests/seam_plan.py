@@ -112,6 +112,7 @@ def project_fused(B, N, D, r, num_cus=NOMINAL_CUS):
                 {"owned": PJ_CHUNK_B, "streamed": max(rw for _, _, _, rw in launches)}, ("prj", part + xp),
                 B * N * 8)
     plan.launches = launches
+    plan.PB, plan.RP, plan.DP = PB, RP, DP  # the instantiation's tile (tests/ladder_plan.py)
     return plan
 
 

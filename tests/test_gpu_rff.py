@@ -47,7 +47,11 @@ def spot_rows(N, rng, k=200, panel_rows=None):
     return np.unique(np.concatenate([[0, N - 1], rng.choice(N, k, replace=False), seams]).astype(np.int64))
 
 
-def check_case(D, S, L, N, dtype, layout, route, monkeypatch, theta_kind="se", lscale=1.0, seed=0):
+def check_case(D, S, L, N, dtype, layout, route, monkeypatch, theta_kind="se", lscale=1.0, seed=0, twice=False,
+               report=None, all_rows=False):
+    """`twice`: both entry points are called a second time and must return the same bits.  `report`: a dict that
+    receives the worst error / bound of the features and of the samples.  `all_rows`: every row of both results is
+    compared with long double, not the rows of `spot_rows` (the default, for the large N of the cases below)."""
     from cggp import kernels, ops, rff
 
     rng = np.random.default_rng(seed)
@@ -72,11 +76,16 @@ def check_case(D, S, L, N, dtype, layout, route, monkeypatch, theta_kind="se", l
     torch.cuda.synchronize()
     assert out.shape == ((S, N) if layout == ops.ROWS else (N, S))
     assert phi.shape == (N, 2 * L)
+    if twice:
+        assert torch.equal(ops.rff_sample(Xd, thd, Wd, scale, layout), out)
+        assert torch.equal(ops.rff_features(Xd, thd), phi)
     if N == 0:
         return None
     u = U[dtype]
     # rows of Phi per panel: 2^28 / (2 L elem) (csrc/rff.hip, sample_panel_t): 16384 at fp64 and 32768 at fp32 for L = 1024
     rows = spot_rows(N, rng, panel_rows=(1 << 28) // (2 * L * (4 if dtype == torch.float32 else 8)) if L else None)
+    if all_rows:
+        rows = np.arange(N, dtype=np.int64)
     cos, sin, Pabs = exact_parts(X, th, rows)
     # features
     feat_bound = 8 * u * (1 + Pabs)
@@ -91,6 +100,9 @@ def check_case(D, S, L, N, dtype, layout, route, monkeypatch, theta_kind="se", l
     got = out.double().cpu().numpy()
     got = got[:, rows] if layout == ops.ROWS else got[rows].T
     err = np.abs(got - ref.astype(np.float64))
+    if report is not None:
+        report["features"] = float(np.max(np.maximum(np.abs(ph[:, :L] - cos), np.abs(ph[:, L:] - sin)) / feat_bound))
+        report["samples"] = float(np.max(err / bound))
     assert np.all(err <= bound), (D, S, L, N, str(dtype), route, float(np.max(err / bound)))
     return float(np.max(Pabs))
 

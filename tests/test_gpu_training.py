@@ -13,6 +13,8 @@ from oracle import cluster as oc, kernels as ok, models as om
 
 pytestmark = pytest.mark.gpu
 KINDS = ["se", "matern12", "matern32", "matern52"]
+# mgp_k_dense_vjp against long double, of the sum of |terms| (shared with tests/test_gpu_ladder.py)
+DENSE_VJP_BARS = ((torch.float64, 1e-10), (torch.float32, 2e-4))
 
 
 def dev():
@@ -101,7 +103,7 @@ def test_k_dense_vjp_against_long_double(name, D):
         spec = ops.KernelSpec(name, 1.4, ls.tolist(), D)
         rv, rl, sv, sl = k_dense_vjp_reference(name, 1.4, ls, A, B, G)
         rv, sv, rl, sl = float(rv), float(sv), rl.astype(np.float64), sl.astype(np.float64)
-        for dtype, bar in ((torch.float64, 1e-10), (torch.float32, 2e-4)):
+        for dtype, bar in DENSE_VJP_BARS:
             dv, dl = ops.k_dense_vjp(spec, T(A).to(dtype), T(B).to(dtype), T(G).to(dtype))
             dl = np.asarray(dl)
             assert np.isfinite(dv) and np.all(np.isfinite(dl)), (na, nb, dtype)
