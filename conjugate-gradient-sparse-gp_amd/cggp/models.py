@@ -31,6 +31,21 @@ def rademacher(shape, dtype, device, seed):
     return torch.from_numpy(z.astype(np.float64)).to(device=device, dtype=dtype)
 
 
+DATA_TERMS = ("batch", "trace")
+
+
+def check_data_term(data_term, dtype, D, trainable_inducing=False):
+    """The constructor checks of `data_term`, shared by `CGGP` and `training.TrainableCGGP`."""
+    if data_term not in DATA_TERMS:
+        raise ValueError(f"data_term must be one of {DATA_TERMS}, got {data_term!r}")
+    if data_term == "trace":
+        if dtype != torch.float64:
+            raise ValueError(f'data_term="trace" is fp64 only, got {dtype}')
+        if trainable_inducing and D > 32:
+            raise ValueError(f'data_term="trace" with trainable_inducing=True needs D <= 32, got D={D}')
+    return data_term
+
+
 class _EvalLogdet(torch.autograd.Function):
     """`eval_logdet` custom gradient (`cggp/models.py:26-46`): forward 0.0, backward
     df * CG(K, I)^T (exact) or CG(K, Zp) (df Zp)^T / P (probes)."""
@@ -259,14 +274,25 @@ class CGGP(ClusterGP):
     argument of every `KmmLambdaOperator` the model makes: False the sweep form, True libmgp's many-column form
     (each kernel value evaluated once per 256 columns and contracted on the fp64 matrix cores: the form for
     `W = CG(K_mm + Lambda, K_mn)`, one column per test row), "auto" the many-column form from
-    `conjugate_gradient.WIDE_MIN_COLUMNS` columns and `WIDE_MIN_M` inducing points on."""
+    `conjugate_gradient.WIDE_MIN_COLUMNS` columns and `WIDE_MIN_M` inducing points on.
+
+    `data_term` ("batch", the default and the reference's form, or "trace"; fp64 only) is what `elbo(data)` does with
+    the rows of `data`.  "batch" solves `W = CG(K_mm + Lambda, K_mn)` with one column per row to sum the diagonal of
+    `K_nm W`.  "trace" takes that sum as a trace, `B variance - tr(A^-1 K_mn K_nm)`, and estimates it with the probes
+    of the KL term: `(1/P) sum_p (K_nm s_p) . (K_nm z_p)` with `s_p = A^-1 z_p` the solves `prior_kl` makes anyway, so
+    every solve has `1 + P` columns and the rows of `data` enter through one `mgp_knm_matvec` pass on `[a | S | Zp]`;
+    nothing [M, B] is formed, for a minibatch or the whole data set.  With `num_probes=None` and no
+    `probes` the dense model takes the exact trace from `Q = K_mn K_nm` (`mgp_kmn_knm`) and one M-column solve; the
+    matrix-free model refuses that, as above.  Value only: `training.TrainableCGGP` is the differentiable form."""
 
     def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, matrix_free=False,
-                 wide_solves=False, **kwargs):
+                 wide_solves=False, data_term="batch", **kwargs):
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
         super().__init__(kernel, likelihood, inducing_variable, **kwargs)
+        Z = self.inducing_variable.Z
+        self.data_term = check_data_term(data_term, Z.dtype, Z.shape[1])
         self.conjugate_gradient = conjugate_gradient
         self.num_probes = num_probes
         self.probe_seed = 0
@@ -365,7 +391,50 @@ class CGGP(ClusterGP):
             means.append(ops.knm_matvec(spec, xb, Z, a) + self._mean(xb))
         return torch.cat(means, 0), torch.cat(variances, 0)
 
+    def _elbo_trace(self, data, probes):
+        """`elbo` with `data_term="trace"`: the sum of the predictive variances as B variance - tr(A^-1 K_mn K_nm),
+        estimated with the probes of the KL term (or exact, from Q = K_mn K_nm, in the dense model without probes)."""
+        x, y = data
+        exact = self.num_probes is None and probes is None
+        if self.matrix_free and exact:
+            raise ValueError("matrix_free=True needs num_probes (or probes=): the exact trace solves M right-hand sides")
+        Z, cg = self.inducing_variable.Z, self.conjugate_gradient
+        spec = self.kernel.spec(Z.shape[1])
+        B, s2, variance = x.shape[0], float(self.likelihood.variance), float(self.kernel.variance)
+        scale = self.scale(B) if B else 1.0  # without rows the data term is 0 whatever multiplies it
+        Kmm, KmmLambda, times_kmm = self._system()
+        a = cg(KmmLambda, self.pseudo_u)  # :303 / :339
+        at = a.t().contiguous()
+        quad = ops.dot_all(times_kmm(at), at)  # :316-317
+        const = torch.log(self.diag_variance).sum().item()  # :321
+        if exact:
+            # tr(A^-1 K_mm) of the KL term and (scale / s2) tr(A^-1 Q) of the data term from one M-column solve
+            rhs = Kmm + (scale / s2) * ops.kmn_knm(spec, x, Z) if B else Kmm
+            both = cg(KmmLambda, rhs).diagonal().sum().item()
+            if B == 0:
+                return 0.5 * both - 0.5 * (quad - const)
+            fmu = ops.knm_matvec(spec, x, Z, a) + self._mean(x)
+            resid = (y - fmu).contiguous()
+            data_sum = -0.5 * B * math.log(2.0 * math.pi * s2) - 0.5 * (ops.dot_all(resid, resid) + B * variance) / s2
+            return scale * data_sum + 0.5 * both - 0.5 * (quad - const)
+        if probes is None:
+            probes = rademacher((Z.shape[0], self.num_probes), Z.dtype, Z.device, self.probe_seed)
+            self.probe_seed += 1
+        P = probes.shape[1]
+        S = cg(KmmLambda, probes)  # :311
+        trace = ops.dot_all(S.t().contiguous(), times_kmm(probes.t().contiguous())) / P  # :312-314
+        kl = 0.5 * (quad - trace - const)  # eval_logdet's forward value is 0.0
+        if B == 0:
+            return -kl
+        out = ops.knm_matvec(spec, x, Z, torch.cat([a, S, probes], dim=1).contiguous())  # [mu | U | V], [B, 2 P + 1]
+        resid = (y - (out[:, :1] + self._mean(x))).contiguous()
+        uv = ops.dot_all(out[:, 1:1 + P].contiguous(), out[:, 1 + P:].contiguous()) / P  # ~ tr(A^-1 K_mn K_nm)
+        data_sum = -0.5 * B * math.log(2.0 * math.pi * s2) - 0.5 * (ops.dot_all(resid, resid) + B * variance - uv) / s2
+        return scale * data_sum - kl
+
     def elbo(self, data, probes=None):
+        if self.data_term == "trace":
+            return self._elbo_trace(data, probes)
         x, y = data
         kl = self.prior_kl(probes=probes)
         f_mean, f_var = self.predict_f(x, full_cov=False, full_output_cov=False)

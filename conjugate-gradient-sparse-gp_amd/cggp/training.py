@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from . import ops
 from .conjugate_gradient import ConjugateGradient
 from .kernels import Stationary
-from .models import eval_logdet, rademacher
+from .models import check_data_term, eval_logdet, rademacher
 
 
 class Parameter:
@@ -237,6 +237,78 @@ class _KzzLambdaLogdet(torch.autograd.Function):
         return grads[:len(ctx.needs_input_grad)]  # `wide` is optional in apply()
 
 
+PANEL_BYTES = 256 << 20  # the largest row panel of a [B, M] cotangent that `_knm_theta_grads_panels` forms
+
+
+def _knm_theta_grads_panels(spec, x, Z, G, V):
+    """(dvariance, [dl_d]) of sum(G o (k(x, Z) V)) for G [B, R], V [M, R] at any D <= 512: row panels of the cotangent
+    W = G V^T of at most `PANEL_BYTES` through `mgp_k_dense_vjp`, added in row order.  No dZ on this route."""
+    B, M = x.shape[0], Z.shape[0]
+    rows = max(1, PANEL_BYTES // (8 * M))
+    dvar, dls = 0.0, [0.0] * spec.D
+    Vt = V.t().contiguous()
+    for i0 in range(0, B, rows):
+        pv, pl = ops.k_dense_vjp(spec, x[i0:i0 + rows], Z, G[i0:i0 + rows] @ Vt)
+        dvar += pv
+        dls = [s + p for s, p in zip(dls, pl)]
+    return dvar, dls
+
+
+class _KnmTimes(torch.autograd.Function):
+    """k(x, Z) [V | C] for V [M, R], C [M, Rc] (C a constant: the probes), the [B, M] block never formed: forward ONE
+    `mgp_knm_matvec` on the R + Rc columns.  Backward at G [B, R + Rc]: dV = k(Z, x) G[:, :R] by `mgp_kmn_matvec`, and
+    (dvariance, dlengthscales, dZ) by ONE `mgp_kmn_knm_vjp` call with Gq = NULL, Y = G and Gb = [V | C] -- the cotangent
+    of the block is G [V | C]^T, of rank R + Rc.  D > 32 (which that entry point refuses): dvariance and dlengthscales
+    by `_knm_theta_grads_panels`; a Z that needs a gradient there is refused at the model's construction."""
+
+    @staticmethod
+    def forward(ctx, variance, lengthscales, Z, V, C, x, kind):
+        ctx.spec = ops.KernelSpec(kind, float(variance), [float(v) for v in lengthscales.reshape(-1)], Z.shape[1])
+        ctx.v_shape, ctx.l_shape, ctx.live = variance.shape, lengthscales.shape, V.shape[1]
+        VC = torch.cat([V.detach(), C.detach()], dim=1).contiguous()
+        Zd = Z.detach()
+        ctx.save_for_backward(Zd, VC, x)
+        return ops.knm_matvec(ctx.spec, x, Zd, VC)
+
+    @staticmethod
+    def backward(ctx, G):
+        Zd, VC, x = ctx.saved_tensors
+        G = G.contiguous()
+        spec, need_z = ctx.spec, ctx.needs_input_grad[2]
+        if spec.D <= 32:
+            dvar, dls, dZ = ops.kmn_knm_vjp(spec, x, Zd, None, G, VC, need_dZ=need_z)
+        else:
+            if need_z:
+                raise ValueError(f"the trace form's gradient in Z needs D <= 32, got D={spec.D}")
+            dvar, dls = _knm_theta_grads_panels(spec, x, Zd, G, VC)
+            dZ = None
+        gv, gl = _theta_grads(dvar, dls, ctx.v_shape, ctx.l_shape)
+        dV = None
+        if ctx.needs_input_grad[3]:
+            dV = ops.kmn_matvec(spec, x, Zd, G[:, :ctx.live].contiguous())
+        return gv, gl, dZ, dV, None, None, None
+
+
+class _KmnKnm(torch.autograd.Function):
+    """Q = k(Z, x) k(x, Z) [M, M] by `mgp_kmn_knm`; backward `mgp_kmn_knm_vjp` with the dense cotangent Gq, as
+    `_SGPRElbo` (fp64, D <= 32)."""
+
+    @staticmethod
+    def forward(ctx, variance, lengthscales, Z, x, kind):
+        ctx.spec = ops.KernelSpec(kind, float(variance), [float(v) for v in lengthscales.reshape(-1)], Z.shape[1])
+        ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
+        Zd = Z.detach()
+        ctx.save_for_backward(Zd, x)
+        return ops.kmn_knm(ctx.spec, x, Zd)
+
+    @staticmethod
+    def backward(ctx, G):
+        Zd, x = ctx.saved_tensors
+        dvar, dls, dZ = ops.kmn_knm_vjp(ctx.spec, x, Zd, G.contiguous(), need_dZ=ctx.needs_input_grad[2])
+        gv, gl = _theta_grads(dvar, dls, ctx.v_shape, ctx.l_shape)
+        return gv, gl, dZ, None, None
+
+
 class TrainableCGGP:
     """Differentiable `CGGP.elbo` (`cggp/models.py:125-134,293-354`).
 
@@ -261,15 +333,35 @@ class TrainableCGGP:
     `k_grad_points` (any D); with `matrix_free=True` each of the three nodes makes one `mgp_kmn_knm_vjp` call on (Z, Z)
     with a rank-2R cotangent (fp64, D <= 32: `ValueError` at construction beyond).  `pseudo_u` and `cluster_counts`
     stay frozen (`models.py:220`).  The reference's `--tip` flow passes `update_fn=None`; replacing `model.Z` from an
-    `update_fn` while it is trainable is not supported (the optimiser would keep stepping the old leaf)."""
+    `update_fn` while it is trainable is not supported (the optimiser would keep stepping the old leaf).
+
+    `data_term="trace"` (default "batch": everything above, the reference's form): the sum of the rows'
+    predictive variances enters as `B variance - tr(A^-1 K_mn K_nm)`, A = K_mm + Lambda, and the trace is estimated
+    with the probes Zp of the KL term, whose solves S = A^-1 Zp are shared:
+
+        [mu | U | V] = K_nm [a | S | Zp],    sum_n var_exp_n = -(B/2) log(2 pi s2)
+                                                 - (|y - mu|^2 + B variance - (1/P) sum_p U_p . V_p) / (2 s2)
+
+    so every solve has 1 + P columns whatever B is, the rows pass through `_KnmTimes` (`mgp_knm_matvec` forward;
+    `mgp_kmn_matvec` and ONE `mgp_kmn_knm_vjp` call of 2 P + 1 columns backward) and nothing [M, B] is formed: this is
+    the form for the full data set (`train_using_lbfgs_and_update`) and works on a minibatch alike.  KL, scale, the
+    log-det node and the probe handling are those of "batch"; `fused_solves=True` sends [pseudo_u | probes] through
+    one solve; `wide_solves` has nothing to widen.  With exact probes (`probes = sqrt(M) I`) it equals "batch"; with P
+    Rademacher probes it is an unbiased estimate of it (the README gives the spread).  `num_probes=None` without
+    `probes=`: the dense model forms Q = K_mn K_nm (`mgp_kmn_knm`, D <= 32) and takes both traces from one M-column
+    solve, tr(A^-1 (K_mm + (scale / s2) Q)), which equals "batch" at `num_probes=None`; the matrix-free model raises
+    `ValueError`, as above.  fp64 only.  D > 32: variance, lengthscales and noise only -- the kernel gradient then
+    walks row panels of the rank-(2 P + 1) cotangent (at most 256 MiB) through `mgp_k_dense_vjp`; with
+    `trainable_inducing=True` that is a `ValueError` at construction."""
 
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
                  num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
-                 wide_solves=False, trainable_inducing=False):
+                 wide_solves=False, trainable_inducing=False, data_term="batch"):
         from .conjugate_gradient import check_wide
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
+        self.data_term = check_data_term(data_term, Z.dtype, Z.shape[1], trainable_inducing)
         self.kernel = kernel if isinstance(kernel, TrainableKernel) else TrainableKernel(kernel)
         self.noise_p = Parameter(noise_variance)
         self.trainable_inducing = bool(trainable_inducing)
@@ -340,7 +432,78 @@ class TrainableCGGP:
         scale = 1.0 if self.num_data is None else float(self.num_data) / float(x.shape[0])  # :163-169
         return var_exp.sum() * scale - kl
 
+    def _elbo_trace(self, data, probes):
+        """`elbo` with `data_term="trace"`, dense and matrix-free (the class docstring has the formulas)."""
+        x, y = data
+        Z, cg, kind = self.Z, self.conjugate_gradient, self.kernel.name
+        dev, dt, M, B = Z.device, Z.dtype, Z.shape[0], x.shape[0]
+        exact = self.num_probes is None and probes is None
+        if self.matrix_free and exact:
+            raise ValueError("matrix_free=True needs num_probes (or probes=): the exact trace solves M right-hand sides")
+        s2 = self.noise_p().to(device=dev, dtype=dt)
+        var_p, ls = self.kernel.variance_p(), self.kernel.lengthscales_p()
+        if ls.dim() == 0:
+            ls = ls.reshape(1)
+        var_f = var_p.to(device=dev, dtype=dt)
+        lam = s2 / self.cluster_counts[:, 0]  # diag_variance, :226-228
+        if self.matrix_free:
+            wide = self.wide_solves
+            times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind)
+            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide)
+        else:
+            Kmm = self.kernel.K(Z)  # :300 / :333
+            KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
+            times_kzz = lambda V: Kmm @ V
+            solve = lambda rhs: cg(KL, rhs)
+        knm_times = lambda V, C: _KnmTimes.apply(var_p, ls, Z, V, C, x.contiguous(), kind)
+        scale = 1.0 if self.num_data is None or B == 0 else float(self.num_data) / float(B)  # :163-169
+        const = torch.log(lam).sum()  # :321
+        log_norm = -0.5 * B * (math.log(2.0 * math.pi) + torch.log(s2))
+        if exact:  # the dense model alone
+            a = solve(self.pseudo_u)  # :303 / :339
+            quad = (times_kzz(a) * a).sum()  # :316-317
+            logdet = eval_logdet(KL, cg, None, None)  # :319
+            if B == 0:
+                return 0.5 * torch.diagonal(solve(Kmm)).sum() - 0.5 * (quad + logdet - const)  # :304-306
+            # tr(A^-1 K_mm) of the KL term and (scale / s2) tr(A^-1 Q) of the data term from one M-column solve
+            Q = _KmnKnm.apply(var_p, ls, Z, x.contiguous(), kind)
+            both = torch.diagonal(solve(Kmm + (scale / s2) * Q)).sum()
+            fmu = knm_times(a, a.new_empty((M, 0)))
+            data_sum = log_norm - 0.5 * (((y - fmu) ** 2).sum() + B * var_f) / s2
+            return data_sum * scale + 0.5 * both - 0.5 * (quad + logdet - const)
+        if probes is None:
+            probes = rademacher((M, self.num_probes), dt, dev, self.probe_seed)
+            self.probe_seed += 1
+        P = probes.shape[1]
+        if self.fused_solves:
+            sol = solve(torch.cat([self.pseudo_u, probes], dim=1))  # :303 / :339 and :311 in one solve
+            a, S = sol[:, :1], sol[:, 1:]
+        else:
+            a, S = solve(self.pseudo_u), solve(probes)  # :303 / :339, :311
+        trace = (S * times_kzz(probes)).sum() / P  # :312-314
+        quad = (times_kzz(a) * a).sum()  # :316-317
+        own = None
+        if self.independent_logdet_probes:
+            own = rademacher((M, P), dt, dev, self.logdet_probe_seed)  # fresh draw, :38-39
+            self.logdet_probe_seed += 1
+        if self.matrix_free:  # solved in the backward pass from `own`, else K^-1 Zp reused
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None if own is not None else S.detach(),
+                                            probes if own is None else own, Z, kind, cg, wide)
+        elif own is not None:
+            logdet = eval_logdet(KL, cg, P, own)  # second probe solve in the backward pass, :40-42
+        else:
+            logdet = _LogdetFromSolution.apply(KL, S.detach(), probes)  # :319 with K^-1 Zp reused
+        kl = 0.5 * (quad - trace + logdet - const)
+        if B == 0:
+            return -kl
+        out = knm_times(torch.cat([a, S], dim=1), probes)  # [mu | U | V], [B, 2 P + 1]
+        fmu, U, V = out[:, :1], out[:, 1:1 + P], out[:, 1 + P:]
+        data_sum = log_norm - 0.5 * (((y - fmu) ** 2).sum() + B * var_f - (U * V).sum() / P) / s2
+        return data_sum * scale - kl
+
     def elbo(self, data, probes=None):
+        if self.data_term == "trace":
+            return self._elbo_trace(data, probes)
         if self.matrix_free:
             return self._elbo_matrix_free(data, probes)
         x, y = data
@@ -402,7 +565,8 @@ class TrainableCGGP:
         Z = self.Z.detach().clone() if self.trainable_inducing else self.Z
         return CGGP(self.kernel.frozen(), self.noise_p.value, Z, self.conjugate_gradient,
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
-                    num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves)
+                    num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves,
+                    data_term=self.data_term)
 
 
 class _GPRLmlEstimate(torch.autograd.Function):
