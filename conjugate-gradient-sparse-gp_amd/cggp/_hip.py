@@ -161,6 +161,11 @@ SIGNATURES = {
     "mgp_covertree_level_rows": (_I, [_P, _I, _P, _P]),
 }
 
+# entry points declared in include/mgp_pathwise.h (same library; tests/test_abi_pathwise.py checks this table)
+EXT_SIGNATURES = {
+    "mgp_rff_sample_vjp": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, ctypes.c_int32, _D, _P, _I, _P, _P]),
+}
+
 
 def lib_path():
     # MGP_LIBRARY lets A/B measurements load an experimental build; the default is the in-tree one
@@ -179,7 +184,7 @@ def load_library():
                 f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C conjugate-gradient-sparse-gp_amd/csrc`).  There is no CPU fallback.")
         lib = ctypes.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

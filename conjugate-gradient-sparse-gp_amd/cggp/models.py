@@ -31,19 +31,45 @@ def rademacher(shape, dtype, device, seed):
     return torch.from_numpy(z.astype(np.float64)).to(device=device, dtype=dtype)
 
 
-DATA_TERMS = ("batch", "trace")
+DATA_TERMS = ("batch", "trace", "pathwise")
 
 
 def check_data_term(data_term, dtype, D, trainable_inducing=False):
     """The constructor checks of `data_term`, shared by `CGGP` and `training.TrainableCGGP`."""
     if data_term not in DATA_TERMS:
         raise ValueError(f"data_term must be one of {DATA_TERMS}, got {data_term!r}")
-    if data_term == "trace":
+    if data_term != "batch":
         if dtype != torch.float64:
-            raise ValueError(f'data_term="trace" is fp64 only, got {dtype}')
+            raise ValueError(f'data_term="{data_term}" is fp64 only, got {dtype}')
         if trainable_inducing and D > 32:
-            raise ValueError(f'data_term="trace" with trainable_inducing=True needs D <= 32, got D={D}')
+            raise ValueError(f'data_term="{data_term}" with trainable_inducing=True needs D <= 32, got D={D}')
     return data_term
+
+
+def check_pathwise(num_bases, num_samples, epsilon):
+    """The constructor checks of the `data_term="pathwise"` arguments, shared like `check_data_term`."""
+    if int(num_bases) != num_bases or num_bases < 1:
+        raise ValueError(f"num_bases must be a positive integer, got {num_bases!r}")
+    if int(num_samples) != num_samples or num_samples < 1:
+        raise ValueError(f"num_samples must be a positive integer, got {num_samples!r}")
+    if epsilon not in ("reference", "matheron"):
+        raise ValueError(f"epsilon must be one of ('reference', 'matheron'), got {epsilon!r}")
+    return int(num_bases), int(num_samples), epsilon
+
+
+def draw_pathwise(kernel_name, D, M, num_bases, num_samples, seed):
+    """(E [L, D], W [S, 2L], xi [S, M]) float64 CPU tensors, the draws of one `data_term="pathwise"` evaluation, in the
+    stream order of `PathwiseClusterGP.pathwise_samples` (numpy PCG64 from `seed`: bases, weights, noise).  E is the
+    base draw of the frequencies at unit lengthscales, Matern factor sqrt(nu / chi2) included
+    (`rff.basis_theta_parameter`): theta = E / lengthscales is the reparameterisation the bound differentiates."""
+    from . import kernels, rff
+    cls = {"se": kernels.SquaredExponential, "matern12": kernels.Matern12, "matern32": kernels.Matern32,
+           "matern52": kernels.Matern52}[kernel_name]
+    rng = np.random.default_rng(seed)
+    E = rff.basis_theta_parameter(cls(variance=1.0, lengthscales=[1.0] * int(D)), num_bases, rng, dim=int(D))
+    W = rff.rff_weights(num_samples, num_bases, rng)
+    xi = torch.from_numpy(rng.standard_normal((int(num_samples), int(M))))
+    return E, W, xi
 
 
 class _EvalLogdet(torch.autograd.Function):
@@ -283,16 +309,24 @@ class CGGP(ClusterGP):
     every solve has `1 + P` columns and the rows of `data` enter through one `mgp_knm_matvec` pass on `[a | S | Zp]`;
     nothing [M, B] is formed, for a minibatch or the whole data set.  With `num_probes=None` and no
     `probes` the dense model takes the exact trace from `Q = K_mn K_nm` (`mgp_kmn_knm`) and one M-column solve; the
-    matrix-free model refuses that, as above.  Value only: `training.TrainableCGGP` is the differentiable form."""
+    matrix-free model refuses that, as above.  "pathwise" takes the likelihood term from `num_samples` pathwise
+    posterior samples on `num_bases` random Fourier features, `-(1/2) [sum_sn (y_n - f_sn)^2 / (S s2) + B log(2 pi s2)]`
+    (`PathwiseClusterGP`'s estimator with the model's CG and its KL term): one S-column solve whatever B is,
+    never negative in its quadratic part, and with `epsilon="matheron"` (the default here; "reference" as in
+    `pathwise_epsilon`) its expectation is the "batch" data term up to the random-feature truncation.  The draws come
+    from `pathwise_seed`, which advances per call, or are injected as `elbo(data, pathwise=(E, W, xi))`
+    (`draw_pathwise`).  Value only: `training.TrainableCGGP` is the differentiable form."""
 
     def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, matrix_free=False,
-                 wide_solves=False, data_term="batch", **kwargs):
+                 wide_solves=False, data_term="batch", num_bases=1024, num_samples=5, epsilon="matheron", **kwargs):
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
         super().__init__(kernel, likelihood, inducing_variable, **kwargs)
         Z = self.inducing_variable.Z
         self.data_term = check_data_term(data_term, Z.dtype, Z.shape[1])
+        self.num_bases, self.num_samples, self.epsilon = check_pathwise(num_bases, num_samples, epsilon)
+        self.pathwise_seed = 0
         self.conjugate_gradient = conjugate_gradient
         self.num_probes = num_probes
         self.probe_seed = 0
@@ -432,9 +466,42 @@ class CGGP(ClusterGP):
         data_sum = -0.5 * B * math.log(2.0 * math.pi * s2) - 0.5 * (ops.dot_all(resid, resid) + B * variance - uv) / s2
         return scale * data_sum - kl
 
-    def elbo(self, data, probes=None):
+    def _elbo_pathwise(self, data, probes, pathwise):
+        """`elbo` with `data_term="pathwise"`: the likelihood term from S pathwise posterior samples, as
+        `PathwiseClusterGP.compute_likelihood_term`, the [M, M] solve by the model's CG (S columns)."""
+        from . import rff
+        x, y = data
+        Z, cg, kernel = self.inducing_variable.Z, self.conjugate_gradient, self.kernel
+        B, M, D = x.shape[0], Z.shape[0], Z.shape[1]
+        S, L = self.num_samples, self.num_bases
+        if pathwise is None:
+            pathwise = draw_pathwise(kernel.name, D, M, L, S, self.pathwise_seed)
+            self.pathwise_seed += 1
+        kl = self.prior_kl(probes=probes)
+        if B == 0:
+            return -kl
+        E, W, xi = (torch.as_tensor(t).to(device=Z.device, dtype=Z.dtype) for t in pathwise)
+        S, L = W.shape[0], E.shape[0]
+        ls = torch.tensor(kernel.spec(D).lengthscales, dtype=Z.dtype, device=Z.device)
+        theta = (E / ls[None, :]).contiguous()
+        prior = rff.rff_sample(torch.cat([x, Z], dim=0), kernel, L, S, theta=theta, weights=W)  # [S, B + M]
+        lam = self.diag_variance[:, 0]
+        eps = pathwise_epsilon(lam, S, self.epsilon, xi=xi)
+        rhs = (self.pseudo_u[:, 0][None, :] - prior[:, B:] - eps).t().contiguous()  # [M, S]
+        _, KmmLambda, _ = self._system()
+        w = cg(KmmLambda, rhs)
+        f = prior[:, :B] + ops.knm_matvec(kernel.spec(D), x, Z, w.contiguous(), ops.COLS, ops.ROWS)  # [S, B]
+        s2 = float(self.likelihood.variance)
+        mean = self._mean(x)
+        resid = (y.reshape(1, -1) - (f if self.mean_function is None else f + mean.reshape(1, -1))).contiguous()
+        data_sum = -0.5 * (ops.dot_all(resid, resid) / (S * s2) + B * math.log(2.0 * math.pi * s2))
+        return self.scale(B) * data_sum - kl
+
+    def elbo(self, data, probes=None, pathwise=None):
         if self.data_term == "trace":
             return self._elbo_trace(data, probes)
+        if self.data_term == "pathwise":
+            return self._elbo_pathwise(data, probes, pathwise)
         x, y = data
         kl = self.prior_kl(probes=probes)
         f_mean, f_var = self.predict_f(x, full_cov=False, full_output_cov=False)

@@ -500,3 +500,31 @@ def rff_sample(X, theta, W, scale, out_layout=ROWS):
     hd.check(hd.lib.mgp_rff_sample(hd.h, _hip.dtype_code(X), _hip.ptr(X), N, D, _hip.ptr(theta), L, _hip.ptr(W), S,
                                    float(scale), _hip.ptr(out), out_layout))
     return out
+
+
+def rff_sample_vjp(X, theta, W, scale, G, g_layout=ROWS, want_dtheta=True, want_dX=False):
+    """Backward pass of `rff_sample` at the cotangent G [S, N] (ROWS) or [N, S] (COLS): (dtheta [L, D] or None,
+    dX [N, D] or None) by `mgp_rff_sample_vjp` (include/mgp_pathwise.h), phases as in the forward pass.  fp64,
+    D <= 32 and 1 <= S <= 8 only: libmgp refuses anything else (MgpError).  The derivative in `scale` is
+    sum(G o out) / scale and needs no call."""
+    X = _points(X, "X")
+    theta = _points(theta, "theta", X.shape[1], X.dtype)
+    N, D = X.shape
+    L = theta.shape[0]
+    W = _hip.check_tensor(W, "W", dtype=X.dtype)
+    if W.dim() != 2 or W.shape[1] != 2 * L:
+        raise ValueError(f"W must be [S, 2L={2 * L}], got {tuple(W.shape)}")
+    S = W.shape[0]
+    if g_layout not in (COLS, ROWS):
+        raise ValueError(f"bad g_layout {g_layout}")
+    G = _hip.check_tensor(G, "G", dtype=X.dtype, shape=(S, N) if g_layout == ROWS else (N, S))
+    if not (want_dtheta or want_dX):
+        raise ValueError("rff_sample_vjp: nothing asked for (want_dtheta and want_dX are both False)")
+    dtheta = torch.empty((L, D), dtype=X.dtype, device=X.device) if want_dtheta else None
+    dX = torch.empty((N, D), dtype=X.dtype, device=X.device) if want_dX else None
+    if (N == 0 or not want_dX) and (L == 0 or not want_dtheta):
+        return dtheta, dX  # no element to write; N == 0 or L == 0 with one goes through the C-ABI: libmgp writes the zeros
+    hd =_hip.get_handle(X.device)
+    hd.check(hd.lib.mgp_rff_sample_vjp(hd.h, _hip.dtype_code(X), _hip.ptr(X), N, D, _hip.ptr(theta), L, _hip.ptr(W), S,
+                                       float(scale), _hip.ptr(G), g_layout, _hip.ptr(dtheta), _hip.ptr(dX)))
+    return dtheta, dX

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from . import ops
 from .conjugate_gradient import ConjugateGradient
 from .kernels import Stationary
-from .models import check_data_term, eval_logdet, rademacher
+from .models import check_data_term, check_pathwise, draw_pathwise, eval_logdet, rademacher
 
 
 class Parameter:
@@ -289,6 +289,68 @@ class _KnmTimes(torch.autograd.Function):
         return gv, gl, dZ, dV, None, None, None
 
 
+def _rff_vjp_panels(x, theta, W, scale, G, want_dX=False):
+    """(dtheta [L, D], dX [N, D] or None) of sum(G o rff_sample(x, theta, W, scale)) for G [S, N], by row chunks of at
+    most `PANEL_BYTES` of feature panels [cos | sin] (`rff.basis_vectors`: `mgp_rff_features` on the device, torch on the
+    host): Q = scale ((G^T W_s) o cos - (G^T W_c) o sin), dtheta += Q^T x, dX = Q theta.  The route of `_RffSample`
+    outside `mgp_rff_sample_vjp`'s range (D > 32 or S > 8), and on host tensors the reference of its tests."""
+    from . import rff
+    N, L = x.shape[0], theta.shape[0]
+    rows = max(1, PANEL_BYTES // (16 * max(L, 1)))
+    Wc, Ws = W[:, :L], W[:, L:]
+    dtheta = torch.zeros_like(theta)
+    dX = torch.empty_like(x) if want_dX else None
+    for i0 in range(0, N, rows):
+        xb, Gb = x[i0:i0 + rows].contiguous(), G[:, i0:i0 + rows].t()
+        phi = rff.basis_vectors(xb, theta)
+        Q = scale * ((Gb @ Ws) * phi[:, :L] - (Gb @ Wc) * phi[:, L:])
+        dtheta += Q.t() @ xb
+        if want_dX:
+            dX[i0:i0 + rows] = Q @ theta
+    return dtheta, dX
+
+
+class _RffSample(torch.autograd.Function):
+    """Prior function samples [S, B + M] = scale W Phi([x; Z])^T on random Fourier features, differentiable in the
+    frequencies theta [L, D], in scale (a 0-dim tensor, sqrt(variance / L)) and in Z.  Forward: ONE `mgp_rff_sample` on
+    the B + M rows.  Backward at G [S, B + M]: dtheta from one `mgp_rff_sample_vjp` call on all rows, dZ from a second
+    call on the M rows of Z alone (only when Z needs a gradient), dscale = sum(G o out) / scale by `mgp_dot_all`.
+    D > 32 or S > 8 (which that entry point refuses): `_rff_vjp_panels`."""
+
+    @staticmethod
+    def forward(ctx, theta, scale, x, Z, W):
+        pts = torch.cat([x, Z.detach()], dim=0).contiguous()
+        theta, W = theta.detach().contiguous(), W.contiguous()
+        ctx.scale, ctx.B = float(scale), x.shape[0]
+        out = ops.rff_sample(pts, theta, W, ctx.scale, ops.ROWS)
+        ctx.save_for_backward(pts, theta, W, out, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, G):
+        pts, theta, W, out, scale = ctx.saved_tensors
+        G = G.contiguous()
+        D, S, B = pts.shape[1], W.shape[0], ctx.B
+        fused = D <= 32 and S <= 8
+        need_theta, need_scale, need_z = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        dtheta = dZ = dscale = None
+        if need_theta:
+            if fused:
+                dtheta, _ = ops.rff_sample_vjp(pts, theta, W, ctx.scale, G, ops.ROWS)
+            else:
+                dtheta, _ = _rff_vjp_panels(pts, theta, W, ctx.scale, G)
+        if need_z:
+            Zd, Gz = pts[B:], G[:, B:].contiguous()
+            if fused:
+                _, dZ = ops.rff_sample_vjp(Zd, theta, W, ctx.scale, Gz, ops.ROWS, want_dtheta=False, want_dX=True)
+            else:
+                _, dZ = _rff_vjp_panels(Zd, theta, W, ctx.scale, Gz, want_dX=True)
+        if need_scale:
+            v = ops.dot_all(G, out) / ctx.scale if ctx.scale != 0.0 else 0.0
+            dscale = torch.tensor(v, dtype=scale.dtype, device=scale.device).reshape(scale.shape)
+        return dtheta, dscale, None, dZ, None
+
+
 class _KmnKnm(torch.autograd.Function):
     """Q = k(Z, x) k(x, Z) [M, M] by `mgp_kmn_knm`; backward `mgp_kmn_knm_vjp` with the dense cotangent Gq, as
     `_SGPRElbo` (fp64, D <= 32)."""
@@ -352,16 +414,37 @@ class TrainableCGGP:
     solve, tr(A^-1 (K_mm + (scale / s2) Q)), which equals "batch" at `num_probes=None`; the matrix-free model raises
     `ValueError`, as above.  fp64 only.  D > 32: variance, lengthscales and noise only -- the kernel gradient then
     walks row panels of the rank-(2 P + 1) cotangent (at most 256 MiB) through `mgp_k_dense_vjp`; with
-    `trainable_inducing=True` that is a `ValueError` at construction."""
+    `trainable_inducing=True` that is a `ValueError` at construction.
+
+    `data_term="pathwise"` (the reference's `PathwiseClusterGP.elbo`, `cggp/models.py:357-420`, made
+    trainable): the likelihood term from S = `num_samples` pathwise posterior samples on L = `num_bases` random Fourier
+    features,
+
+        f_s = phi(x) w_s sqrt(variance / L) + K_nm A^-1 (u - phi(Z) w_s sqrt(variance / L) - eps_s),
+        data term = -(1/2) [sum_sn (y_n - f_sn)^2 / (S s2) + B log(2 pi s2)] scale,
+
+    with theta = E / lengthscales the reparameterised frequencies (E the base draws, Matern factor included), the prior
+    draw one `_RffSample` node on [x; Z] (`mgp_rff_sample` forward, `mgp_rff_sample_vjp` backward), eps = sqrt(lam) xi
+    (`epsilon="matheron"`, the default here: the expectation over W and xi is then the "batch" data term up to the
+    random-feature truncation) or lam xi ("reference"), the S-column solve through `_KzzLambdaSolve` or the dense CG and
+    the correction through `_KnmTimes`.  The [M, M] solve has S columns whatever B is, the quadratic part is >= 0 on every
+    draw, and the sum over rows averages itself.  KL, scale, the log-det node and the probe handling are those of the
+    other forms; `fused_solves=True` sends [pseudo_u | probes | u - f_Z - eps] through one solve.  The draws (E, W, xi)
+    come from `pathwise_seed`, which advances per call like `probe_seed`, or are injected as
+    `elbo(data, pathwise=(E, W, xi))` (`draw_pathwise`).  fp64 only; D > 32 or S > 8: the prior draw's backward pass walks
+    row chunks of feature panels (`_rff_vjp_panels`), and `trainable_inducing=True` at D > 32 is a `ValueError`."""
 
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
                  num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
-                 wide_solves=False, trainable_inducing=False, data_term="batch"):
+                 wide_solves=False, trainable_inducing=False, data_term="batch", num_bases=1024, num_samples=5,
+                 epsilon="matheron"):
         from .conjugate_gradient import check_wide
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
         self.data_term = check_data_term(data_term, Z.dtype, Z.shape[1], trainable_inducing)
+        self.num_bases, self.num_samples, self.epsilon = check_pathwise(num_bases, num_samples, epsilon)
+        self.pathwise_seed = 0
         self.kernel = kernel if isinstance(kernel, TrainableKernel) else TrainableKernel(kernel)
         self.noise_p = Parameter(noise_variance)
         self.trainable_inducing = bool(trainable_inducing)
@@ -432,6 +515,44 @@ class TrainableCGGP:
         scale = 1.0 if self.num_data is None else float(self.num_data) / float(x.shape[0])  # :163-169
         return var_exp.sum() * scale - kl
 
+    def _probed_kl(self, probes, solve, times_kzz, KL, lam, var_p, ls, extra=None):
+        """The KL term with Hutchinson probes, shared by the "trace" and "pathwise" forms, dense (KL = K_mm + Lambda)
+        and matrix-free (KL None): (kl, a, S, probes, w) with a = A^-1 pseudo_u, S = A^-1 probes and, when `extra`
+        [M, R] is given, w = A^-1 extra -- further columns of the one solve under `fused_solves`, a solve of their own
+        otherwise."""
+        Z, cg, kind = self.Z, self.conjugate_gradient, self.kernel.name
+        dev, dt, M = Z.device, Z.dtype, Z.shape[0]
+        if probes is None:
+            probes = rademacher((M, self.num_probes), dt, dev, self.probe_seed)
+            self.probe_seed += 1
+        P = probes.shape[1]
+        w = None
+        if self.fused_solves:
+            cols = [self.pseudo_u, probes] + ([] if extra is None else [extra])
+            sol = solve(torch.cat(cols, dim=1))  # :303 / :339 and :311 in one solve
+            a, S = sol[:, :1], sol[:, 1:1 + P]
+            if extra is not None:
+                w = sol[:, 1 + P:]
+        else:
+            a, S = solve(self.pseudo_u), solve(probes)  # :303 / :339, :311
+            if extra is not None:
+                w = solve(extra)
+        trace = (S * times_kzz(probes)).sum() / P  # :312-314
+        quad = (times_kzz(a) * a).sum()  # :316-317
+        own = None
+        if self.independent_logdet_probes:
+            own = rademacher((M, P), dt, dev, self.logdet_probe_seed)  # fresh draw, :38-39
+            self.logdet_probe_seed += 1
+        if self.matrix_free:  # solved in the backward pass from `own`, else K^-1 Zp reused
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None if own is not None else S.detach(),
+                                            probes if own is None else own, Z, kind, cg, self.wide_solves)
+        elif own is not None:
+            logdet = eval_logdet(KL, cg, P, own)  # second probe solve in the backward pass, :40-42
+        else:
+            logdet = _LogdetFromSolution.apply(KL, S.detach(), probes)  # :319 with K^-1 Zp reused
+        const = torch.log(lam).sum()  # :321
+        return 0.5 * (quad - trace + logdet - const), a, S, probes, w
+
     def _elbo_trace(self, data, probes):
         """`elbo` with `data_term="trace"`, dense and matrix-free (the class docstring has the formulas)."""
         x, y = data
@@ -471,29 +592,8 @@ class TrainableCGGP:
             fmu = knm_times(a, a.new_empty((M, 0)))
             data_sum = log_norm - 0.5 * (((y - fmu) ** 2).sum() + B * var_f) / s2
             return data_sum * scale + 0.5 * both - 0.5 * (quad + logdet - const)
-        if probes is None:
-            probes = rademacher((M, self.num_probes), dt, dev, self.probe_seed)
-            self.probe_seed += 1
+        kl, a, S, probes, _ = self._probed_kl(probes, solve, times_kzz, None if self.matrix_free else KL, lam, var_p, ls)
         P = probes.shape[1]
-        if self.fused_solves:
-            sol = solve(torch.cat([self.pseudo_u, probes], dim=1))  # :303 / :339 and :311 in one solve
-            a, S = sol[:, :1], sol[:, 1:]
-        else:
-            a, S = solve(self.pseudo_u), solve(probes)  # :303 / :339, :311
-        trace = (S * times_kzz(probes)).sum() / P  # :312-314
-        quad = (times_kzz(a) * a).sum()  # :316-317
-        own = None
-        if self.independent_logdet_probes:
-            own = rademacher((M, P), dt, dev, self.logdet_probe_seed)  # fresh draw, :38-39
-            self.logdet_probe_seed += 1
-        if self.matrix_free:  # solved in the backward pass from `own`, else K^-1 Zp reused
-            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None if own is not None else S.detach(),
-                                            probes if own is None else own, Z, kind, cg, wide)
-        elif own is not None:
-            logdet = eval_logdet(KL, cg, P, own)  # second probe solve in the backward pass, :40-42
-        else:
-            logdet = _LogdetFromSolution.apply(KL, S.detach(), probes)  # :319 with K^-1 Zp reused
-        kl = 0.5 * (quad - trace + logdet - const)
         if B == 0:
             return -kl
         out = knm_times(torch.cat([a, S], dim=1), probes)  # [mu | U | V], [B, 2 P + 1]
@@ -501,9 +601,69 @@ class TrainableCGGP:
         data_sum = log_norm - 0.5 * (((y - fmu) ** 2).sum() + B * var_f - (U * V).sum() / P) / s2
         return data_sum * scale - kl
 
-    def elbo(self, data, probes=None):
+    def draw_pathwise(self, seed):
+        """(E, W, xi) of one `data_term="pathwise"` evaluation (`models.draw_pathwise`) at the model's sizes."""
+        return draw_pathwise(self.kernel.name, self.Z.shape[1], self.Z.shape[0], self.num_bases, self.num_samples, seed)
+
+    def _elbo_pathwise(self, data, probes, pathwise):
+        """`elbo` with `data_term="pathwise"`, dense and matrix-free (the class docstring has the formulas)."""
+        x, y = data
+        Z, cg, kind = self.Z, self.conjugate_gradient, self.kernel.name
+        dev, dt, M, B, D = Z.device, Z.dtype, Z.shape[0], x.shape[0], Z.shape[1]
+        exact = self.num_probes is None and probes is None
+        if self.matrix_free and exact:
+            raise ValueError("matrix_free=True needs num_probes (or probes=): the exact trace solves M right-hand sides")
+        if pathwise is None:
+            pathwise = self.draw_pathwise(self.pathwise_seed)
+            self.pathwise_seed += 1
+        E, W, xi = (torch.as_tensor(t).to(device=dev, dtype=dt).contiguous() for t in pathwise)
+        L, S = E.shape[0], W.shape[0]
+        if E.shape != (L, D) or W.shape != (S, 2 * L) or xi.shape != (S, M) or L < 1 or S < 1:
+            raise ValueError(f"pathwise=(E [L, D={D}], W [S, 2L], xi [S, M={M}]) expected, got {tuple(E.shape)}, "
+                             f"{tuple(W.shape)}, {tuple(xi.shape)}")
+        s2 = self.noise_p().to(device=dev, dtype=dt)
+        var_p, ls = self.kernel.variance_p(), self.kernel.lengthscales_p()
+        if ls.dim() == 0:
+            ls = ls.reshape(1)
+        lam = s2 / self.cluster_counts[:, 0]  # diag_variance, :226-228
+        KL = None
+        if self.matrix_free:
+            wide = self.wide_solves
+            times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind)
+            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide)
+        else:
+            Kmm = self.kernel.K(Z)  # :300 / :333
+            KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
+            times_kzz = lambda V: Kmm @ V
+            solve = lambda rhs: cg(KL, rhs)
+        rhs = None
+        if B > 0:
+            theta = E / ls.to(device=dev, dtype=dt)[None, :]  # the reparameterised frequencies, reference rff.py:20-45
+            prior = _RffSample.apply(theta, torch.sqrt(var_p / L), x.contiguous(), Z, W)  # [S, B + M], :397-402
+            eps = (torch.sqrt(lam) if self.epsilon == "matheron" else lam)[None, :] * xi  # :404-408
+            rhs = (self.pseudo_u[:, 0][None, :] - prior[:, B:] - eps).t()  # [M, S], :414
+        if exact:  # the dense model alone
+            a = solve(self.pseudo_u)  # :303 / :339
+            quad = (times_kzz(a) * a).sum()  # :316-317
+            trace = torch.diagonal(solve(Kmm)).sum()  # :304-306
+            kl = 0.5 * (quad - trace + eval_logdet(KL, cg, None, None) - torch.log(lam).sum())  # :319-322
+            w = solve(rhs) if B > 0 else None
+        else:
+            kl, _, _, _, w = self._probed_kl(probes, solve, times_kzz, KL, lam, var_p, ls, extra=rhs)
+        if B == 0:
+            return -kl
+        corr = _KnmTimes.apply(var_p, ls, Z, w, w.new_empty((M, 0)), x.contiguous(), kind)  # [B, S], :418
+        f = prior[:, :B] + corr.t()  # :419
+        sq = ((y.reshape(1, -1) - f) ** 2).sum()  # :384-385
+        scale = 1.0 if self.num_data is None else float(self.num_data) / float(B)  # :163-169
+        data_sum = -0.5 * (sq / (S * s2) + B * (math.log(2.0 * math.pi) + torch.log(s2)))  # :386-388
+        return data_sum * scale - kl
+
+    def elbo(self, data, probes=None, pathwise=None):
         if self.data_term == "trace":
             return self._elbo_trace(data, probes)
+        if self.data_term == "pathwise":
+            return self._elbo_pathwise(data, probes, pathwise)
         if self.matrix_free:
             return self._elbo_matrix_free(data, probes)
         x, y = data
@@ -557,8 +717,8 @@ class TrainableCGGP:
         scale = 1.0 if self.num_data is None else float(self.num_data) / float(x.shape[0])  # :163-169
         return var_exp.sum() * scale - kl
 
-    def training_loss(self, data, probes=None):
-        return -self.elbo(data, probes=probes)
+    def training_loss(self, data, probes=None, pathwise=None):
+        return -self.elbo(data, probes=probes, pathwise=pathwise)
 
     def frozen_model(self):
         from .models import CGGP
@@ -566,7 +726,8 @@ class TrainableCGGP:
         return CGGP(self.kernel.frozen(), self.noise_p.value, Z, self.conjugate_gradient,
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
                     num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves,
-                    data_term=self.data_term)
+                    data_term=self.data_term, num_bases=self.num_bases, num_samples=self.num_samples,
+                    epsilon=self.epsilon)
 
 
 class _GPRLmlEstimate(torch.autograd.Function):
@@ -974,7 +1135,8 @@ def train_using_lbfgs_and_update(data, model, max_num_iters, update_fn=None, upd
 
     L-BFGS needs a deterministic objective, so when the model estimates the trace / log-det terms
     with Hutchinson probes the SAME probes (drawn once from `probe_seed`) are used for every
-    evaluation.  Returns scipy's `OptimizeResult` (None when `max_num_iters` is 0, as upstream)."""
+    evaluation; a `data_term="pathwise"` model's draw (from its `pathwise_seed`) is held in the same way.
+    Returns scipy's `OptimizeResult` (None when `max_num_iters` is 0, as upstream)."""
     from scipy.optimize import minimize
 
     params = model.parameters()
@@ -983,6 +1145,10 @@ def train_using_lbfgs_and_update(data, model, max_num_iters, update_fn=None, upd
     probes = None
     if model.num_probes is not None and hasattr(model, "Z"):  # TrainableGPR keeps its own fixed probes
         probes = rademacher((model.Z.shape[0], model.num_probes), model.Z.dtype, model.Z.device, probe_seed)
+    held = {}
+    if getattr(model, "data_term", None) == "pathwise":  # and ONE draw of the bases, weights and noise
+        held["pathwise"] = model.draw_pathwise(model.pathwise_seed)
+        model.pathwise_seed += 1
 
     def assign(flat):
         off = 0
@@ -995,7 +1161,7 @@ def train_using_lbfgs_and_update(data, model, max_num_iters, update_fn=None, upd
         assign(flat)
         for p in params:
             p.grad = None
-        loss = model.training_loss((x, y), probes=probes)
+        loss = model.training_loss((x, y), probes=probes, **held)
         loss.backward()
         g = np.concatenate([p.grad.detach().cpu().numpy().reshape(-1) for p in params])
         return float(loss), g.astype(np.float64)
