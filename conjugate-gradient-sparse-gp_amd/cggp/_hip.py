@@ -166,6 +166,12 @@ EXT_SIGNATURES = {
     "mgp_rff_sample_vjp": (_I, [_P, _I, _P, _L, ctypes.c_int32, _P, _L, _P, ctypes.c_int32, _D, _P, _I, _P, _P]),
 }
 
+# entry points declared in include/mgp_anyd.h (same library; tests/test_anyd_abi.py checks this table)
+ANYD_SIGNATURES = {
+    "mgp_kmn_knm_vjp_anyd": (_I, [_P, _KP, _P, _L, _P, _L, _P, _P, _P, ctypes.c_int32, _L, ctypes.POINTER(_D),
+                                  ctypes.POINTER(_D), _P]),
+}
+
 
 def lib_path():
     # MGP_LIBRARY lets A/B measurements load an experimental build; the default is the in-tree one
@@ -184,7 +190,8 @@ def load_library():
                 f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C conjugate-gradient-sparse-gp_amd/csrc`).  There is no CPU fallback.")
         lib = ctypes.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
+                                  + list(ANYD_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

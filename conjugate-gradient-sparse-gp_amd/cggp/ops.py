@@ -115,6 +115,22 @@ def kmn_knm_vjp(spec, X, Z, Gq, Y=None, Gb=None, need_dZ=False):
     Gb are required (ValueError without them).  X and Z may be the same tensor; with Y = [U | V] and Gb = [V | U] on
     (Z, Z) the cotangent is U V^T + V U^T, so dZ is the whole gradient of sum_r u_r^T k(Z, Z) v_r in Z and dvariance,
     dl are twice `kxx_grad(spec, Z, U, V)`."""
+    return _kmn_knm_vjp(spec, X, Z, Gq, Y, Gb, need_dZ, None)
+
+
+def kmn_knm_vjp_anyd(spec, X, Z, Gq, Y=None, Gb=None, need_dZ=False, panel_rows=0):
+    """`kmn_knm_vjp` at any D <= 512 (`mgp_kmn_knm_vjp_anyd`, include/mgp_anyd.h): the same arguments and the same
+    return.  At D <= 32 it runs `kmn_knm_vjp`'s implementation (the same bits with `panel_rows=0`); above, the kernel
+    panel and the pair kernels stage the dimensions through LDS slice by slice.  `panel_rows`: rows of X per panel,
+    0 = at most 256 MiB of K per panel."""
+    panel_rows = int(panel_rows)
+    if panel_rows < 0:
+        raise ValueError("panel_rows must be >= 0")
+    return _kmn_knm_vjp(spec, X, Z, Gq, Y, Gb, need_dZ, panel_rows)
+
+
+def _kmn_knm_vjp(spec, X, Z, Gq, Y, Gb, need_dZ, panel_rows):
+    """the two wrappers above: `panel_rows=None` calls `mgp_kmn_knm_vjp`, a number `mgp_kmn_knm_vjp_anyd`"""
     X = _points(X, "X", spec.D)
     Z = _points(Z, "Z", spec.D, X.dtype)
     N, M = X.shape[0], Z.shape[0]
@@ -141,9 +157,14 @@ def kmn_knm_vjp(spec, X, Z, Gq, Y=None, Gb=None, need_dZ=False):
     dls = (ctypes.c_double * _hip.MGP_MAX_D)()
     hd = _hip.get_handle(X.device)
     k = spec.struct(_hip.dtype_code(X))
-    hd.check(hd.lib.mgp_kmn_knm_vjp(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(Gq),
-                                    _hip.ptr(Y if P else None), _hip.ptr(Gb if P else None), P, ctypes.byref(dvar),
-                                    dls, _hip.ptr(dZ)))
+    if panel_rows is None:
+        hd.check(hd.lib.mgp_kmn_knm_vjp(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(Gq),
+                                        _hip.ptr(Y if P else None), _hip.ptr(Gb if P else None), P, ctypes.byref(dvar),
+                                        dls, _hip.ptr(dZ)))
+    else:
+        hd.check(hd.lib.mgp_kmn_knm_vjp_anyd(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(Gq),
+                                             _hip.ptr(Y if P else None), _hip.ptr(Gb if P else None), P, panel_rows,
+                                             ctypes.byref(dvar), dls, _hip.ptr(dZ)))
     return dvar.value, [dls[d] for d in range(spec.D)], dZ
 
 

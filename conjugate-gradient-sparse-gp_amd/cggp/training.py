@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import ops
+from . import _hip, ops
 from .conjugate_gradient import ConjugateGradient
 from .kernels import Stationary
 from .models import check_data_term, check_pathwise, draw_pathwise, eval_logdet, rademacher
@@ -962,8 +962,9 @@ class _SGPRElbo(torch.autograd.Function):
     """`models.SGPR.elbo` as an autograd node over (variance, lengthscales, s2, Kmm_j, Z).  Forward: Q by
     `mgp_kmn_knm`, b by `mgp_kmn_matvec`, y^T y, summed over ranks with `allreduce`, then `sgpr_bound`.  Backward:
     `sgpr_bound_adjoints`; the Kmm_j cotangent goes back to the caller (`TrainableKernel.K`, whose backward is
-    `mgp_k_dense_vjp`) and, for a trainable Z, through `kmm_grad_z`; the N-sized part is one `mgp_kmn_knm_vjp` call,
-    and its [dvariance, dl, dZ] partials are summed over ranks by ONE all-reduce."""
+    `mgp_k_dense_vjp`) and, for a trainable Z, through `kmm_grad_z`; the N-sized part is one `mgp_kmn_knm_vjp` call
+    (`mgp_kmn_knm_vjp_anyd` above D = 32), and its [dvariance, dl, dZ] partials are summed over ranks by ONE
+    all-reduce."""
 
     @staticmethod
     def forward(ctx, variance, lengthscales, s2, Kmm_j, Z, model, X, Y):
@@ -996,7 +997,8 @@ class _SGPRElbo(torch.autograd.Function):
         _, Gq, Gb, GK, ds2, dvar = sgpr_bound_adjoints(Kmm_j, Q, b, ctx.yy, s2d, vd, model.num_data)
         need_z = ctx.needs_input_grad[4]
         D, M = spec.D, Zd.shape[0]
-        nv, nl, nz = ops.kmn_knm_vjp(spec, X, Zd, Gq.contiguous(), Y, Gb.contiguous(), need_dZ=need_z)
+        vjp = ops.kmn_knm_vjp_anyd if D > _hip.MGP_FUSED_MAX_D else ops.kmn_knm_vjp  # D <= 32 keeps its entry point
+        nv, nl, nz = vjp(spec, X, Zd, Gq.contiguous(), Y, Gb.contiguous(), need_dZ=need_z)
         if model.allreduce is not None:  # this rank's rows only: one all-reduce of [dvariance, dl, dZ]
             parts = [torch.tensor([nv] + list(nl), dtype=torch.float64, device=X.device)]
             if need_z:
@@ -1025,7 +1027,9 @@ class TrainableSGPR:
     `elbo()` equals `models.SGPR(...).elbo()` at the same values and is an autograd node (`_SGPRElbo`) whose backward
     needs nothing N x M: one `mgp_kmn_knm_vjp` call for the N-sized part.  With `allreduce` (same contract as
     `models.SGPR`: X, Y are this rank's rows) the forward sums Q, K_mn y and y^T y over ranks and the backward makes one
-    all-reduce of its N-sized partials, so every rank ends with the same gradient.  fp64, D <= 32, Y [N, 1]."""
+    all-reduce of its N-sized partials, so every rank ends with the same gradient.  fp64, Y [N, 1]; any D <= 512: above
+    D = 32 the N-sized part is `mgp_kmn_knm_vjp_anyd`, whose kernels stage the dimensions through LDS, and the
+    constructor refuses X, Y, Z that are not on the GPU (ValueError)."""
 
     num_probes = None
     internal_data = True
@@ -1038,8 +1042,12 @@ class TrainableSGPR:
                                  f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
         if X.dim() != 2 or Z.dim() != 2 or Z.shape[1] != X.shape[1]:
             raise ValueError(f"X [N, D] and Z [M, D] expected, got {tuple(X.shape)} and {tuple(Z.shape)}")
-        if X.shape[1] > 32:
-            raise ValueError(f"TrainableSGPR needs D <= 32, got D={X.shape[1]}")
+        if X.shape[1] > _hip.MGP_MAX_D:
+            raise ValueError(f"TrainableSGPR needs D <= {_hip.MGP_MAX_D}, got D={X.shape[1]}")
+        if X.shape[1] > _hip.MGP_FUSED_MAX_D and not (X.is_cuda and Y.is_cuda and Z.is_cuda):
+            # above the fused kernels' D the model is refused here when it cannot run, not at its first backward:
+            # every kernel of the any-D route is device code and there is no host path
+            raise ValueError(f"TrainableSGPR at D={X.shape[1]} > {_hip.MGP_FUSED_MAX_D} needs X, Y and Z on the GPU")
         if Y.dim() != 2 or Y.shape != (X.shape[0], 1):
             raise ValueError(f"Y must be [N={X.shape[0]}, 1], got {tuple(Y.shape)}")
         self.kernel = kernel if isinstance(kernel, TrainableKernel) else TrainableKernel(kernel)

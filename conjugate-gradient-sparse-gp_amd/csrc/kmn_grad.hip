@@ -341,13 +341,13 @@ inline void kvjp_row_blocks(long nr, long nrb_max, long* nrb, long* rpb) {
 
 template <int DP, int KIND>
 int kvjp_rank_fused(mgp_handle* h, const mgp_kernel* k, const double* X, long N, const double* Z, long M,
-                    const double* Y, const double* Gb, int P, double* dvar, double* dls, double* dZ) {
+                    const double* Y, const double* Gb, int P, long panel_rows, double* dvar, double* dls, double* dZ) {
   const int D = k->D;
   SweepParams prm = mgp_make_params(k);
   for (int d = 0; d < MGP_FUSED_MAX_D; ++d) prm.inv_ls[d] = d < D ? 1.0 / k->lengthscales[d] : 0.0;
   constexpr int PCM = kvjp_pc_max(DP, KIND);
-  // row chunk: at most 64 MiB of pack
-  long rows = (long)(((size_t)64 << 20) / ((size_t)(DP + PCM) * 8));
+  // row chunk: at most 64 MiB of pack (panel_rows > 0: that many rows)
+  long rows = panel_rows > 0 ? panel_rows : (long)(((size_t)64 << 20) / ((size_t)(DP + PCM) * 8));
   if (rows > N) rows = N;
   const long ncb = (M + kVjpThreads - 1) / kVjpThreads;
   const long nrb_max = kvjp_max_row_blocks(h, rows, ncb);
@@ -409,13 +409,14 @@ int kvjp_rank_fused(mgp_handle* h, const mgp_kernel* k, const double* X, long N,
 
 template <int DP, int KIND>
 int kvjp_rank_panel(mgp_handle* h, const mgp_kernel* k, const double* X, long N, const double* Z, long M,
-                    const double* Y, const double* Gb, int P, double* dvar, double* dls, double* dZ) {
+                    const double* Y, const double* Gb, int P, long panel_rows, double* dvar, double* dls, double* dZ) {
   const int D = k->D;
   SweepParams prm = mgp_make_params(k);
   for (int d = 0; d < MGP_FUSED_MAX_D; ++d) prm.inv_ls[d] = d < D ? 1.0 / k->lengthscales[d] : 0.0;
-  // row panel: at most 256 MiB of W
+  // row panel: at most 256 MiB of W (panel_rows > 0: that many rows)
   long rows = (long)(((size_t)256 << 20) / ((size_t)M * 8));
   rows = rows < 16 ? 16 : rows / 16 * 16;
+  if (panel_rows > 0) rows = panel_rows;
   if (rows > N) rows = N;
   const long ncb = (M + kVjpThreads - 1) / kVjpThreads;
   const long nrb_max = kvjp_max_row_blocks(h, rows, ncb);
@@ -459,13 +460,14 @@ int kvjp_rank_panel(mgp_handle* h, const mgp_kernel* k, const double* X, long N,
 
 template <int DP, int KIND>
 int kvjp_run(mgp_handle* h, const mgp_kernel* k, const double* X, long N, const double* Z, long M, const double* Gq,
-             const double* Y, const double* Gb, int P, double* dvar, double* dls, double* dZ) {
+             const double* Y, const double* Gb, int P, long panel_rows, double* dvar, double* dls, double* dZ) {
   const int D = k->D;
   SweepParams prm = mgp_make_params(k);
   for (int d = 0; d < MGP_FUSED_MAX_D; ++d) prm.inv_ls[d] = d < D ? 1.0 / k->lengthscales[d] : 0.0;
-  // row panel: at most 256 MiB of K (and as much of W)
+  // row panel: at most 256 MiB of K (and as much of W); panel_rows > 0: that many rows
   long rows = (long)(((size_t)256 << 20) / ((size_t)M * 8));
   rows = rows < 16 ? 16 : rows / 16 * 16;
+  if (panel_rows > 0) rows = panel_rows;
   if (rows > N) rows = N;
   const long ncb = (M + kVjpThreads - 1) / kVjpThreads;
   const long nrb_max = kvjp_max_row_blocks(h, rows, ncb);
@@ -517,15 +519,22 @@ int kvjp_run(mgp_handle* h, const mgp_kernel* k, const double* X, long N, const 
 
 }  // namespace
 
-extern "C" int mgp_kmn_knm_vjp(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
-                               const void* Gq, const void* Y, const void* Gb, int32_t P, double* dvariance,
-                               double* dlengthscales, void* dZ) {
+int mgp_kvjp_symmetrize(mgp_handle* h, const double* Gq, long M, double* G2) {
+  hipLaunchKernelGGL(kvjp_sym_kernel, dim3((unsigned)((M * M + 255) / 256)), dim3(256), 0, h->stream, Gq, M, G2);
+  MGP_LAUNCH_CHECK(h);
+  return MGP_OK;
+}
+
+int mgp_kvjp_check(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
+                   const void* Gq, const void* Y, const void* Gb, int32_t P, int max_d, double* dvariance,
+                   double* dlengthscales, void* dZ, int* done) {
+  *done = 0;
   MGP_TRY(mgp_check_kernel(h, k));
   if (!dvariance || !dlengthscales) return mgp_fail(h, MGP_E_BADARG, "NULL output");
   *dvariance = 0.0;
   for (int d = 0; d < k->D; ++d) dlengthscales[d] = 0.0;
   if (k->dtype != MGP_F64) return mgp_fail(h, MGP_E_DTYPE, "kmn_knm_vjp: fp64 only");
-  if (k->D > MGP_FUSED_MAX_D) return mgp_fail(h, MGP_E_BADARG, "kmn_knm_vjp: D = %d > %d", k->D, MGP_FUSED_MAX_D);
+  if (k->D > max_d) return mgp_fail(h, MGP_E_BADARG, "kmn_knm_vjp: D = %d > %d", k->D, max_d);
   if (N < 0 || M < 1 || P < 0) return mgp_fail(h, MGP_E_SHAPE, "kmn_knm_vjp: N >= 0, M >= 1, P >= 0 required");
   if (!Z) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   if (!Gq && (P < 1 || !Gb)) return mgp_fail(h, MGP_E_BADARG, "kmn_knm_vjp: Gq = NULL needs P >= 1 with Y and Gb");
@@ -534,26 +543,41 @@ extern "C" int mgp_kmn_knm_vjp(mgp_handle* h, const mgp_kernel* k, const void* X
       MGP_HIP(h, hipMemsetAsync(dZ, 0, (size_t)M * k->D * 8, h->stream));
       MGP_HIP(h, hipStreamSynchronize(h->stream));
     }
+    *done = 1;
     return MGP_OK;
   }
   if (!X) return mgp_fail(h, MGP_E_BADARG, "NULL data pointer");
   if (P > 0 && (!Y || !Gb)) return mgp_fail(h, MGP_E_BADARG, "kmn_knm_vjp: P > 0 needs Y and Gb");
-  const double *Xd = (const double*)X, *Zd = (const double*)Z, *Gqd = (const double*)Gq;
-  const double *Yd = P > 0 ? (const double*)Y : nullptr, *Gbd = P > 0 ? (const double*)Gb : nullptr;
-  double* dZd = (double*)dZ;
-  if (!Gq)  // W = Y Gb^T alone: fused up to kVjpPFused columns, row panels of W beyond
+  return MGP_OK;
+}
+
+int mgp_kvjp_fused_d(mgp_handle* h, const mgp_kernel* k, const double* Xd, long N, const double* Zd, long M,
+                     const double* Gqd, const double* Yd, const double* Gbd, int P, long panel_rows, double* dvariance,
+                     double* dlengthscales, double* dZd) {
+  if (!Gqd)  // W = Y Gb^T alone: fused up to kVjpPFused columns, row panels of W beyond
     return mgp_with_kind(k->kind, [&](auto kind) {
       return mgp_with_dp<4>(k->D, [&](auto dp) {
         constexpr int DP = decltype(dp)::value, KIND = decltype(kind)::value;
         if (P <= kVjpPFused)
-          return kvjp_rank_fused<DP, KIND>(h, k, Xd, N, Zd, M, Yd, Gbd, P, dvariance, dlengthscales, dZd);
-        return kvjp_rank_panel<DP, KIND>(h, k, Xd, N, Zd, M, Yd, Gbd, P, dvariance, dlengthscales, dZd);
+          return kvjp_rank_fused<DP, KIND>(h, k, Xd, N, Zd, M, Yd, Gbd, P, panel_rows, dvariance, dlengthscales, dZd);
+        return kvjp_rank_panel<DP, KIND>(h, k, Xd, N, Zd, M, Yd, Gbd, P, panel_rows, dvariance, dlengthscales, dZd);
       });
     });
   return mgp_with_kind(k->kind, [&](auto kind) {
     return mgp_with_dp<4>(k->D, [&](auto dp) {
-      return kvjp_run<decltype(dp)::value, decltype(kind)::value>(h, k, Xd, N, Zd, M, Gqd, Yd, Gbd, P, dvariance,
-                                                                  dlengthscales, dZd);
+      return kvjp_run<decltype(dp)::value, decltype(kind)::value>(h, k, Xd, N, Zd, M, Gqd, Yd, Gbd, P, panel_rows,
+                                                                  dvariance, dlengthscales, dZd);
     });
   });
+}
+
+extern "C" int mgp_kmn_knm_vjp(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
+                               const void* Gq, const void* Y, const void* Gb, int32_t P, double* dvariance,
+                               double* dlengthscales, void* dZ) {
+  int done = 0;
+  MGP_TRY(mgp_kvjp_check(h, k, X, N, Z, M, Gq, Y, Gb, P, MGP_FUSED_MAX_D, dvariance, dlengthscales, dZ, &done));
+  if (done) return MGP_OK;
+  return mgp_kvjp_fused_d(h, k, (const double*)X, N, (const double*)Z, M, (const double*)Gq,
+                          P > 0 ? (const double*)Y : nullptr, P > 0 ? (const double*)Gb : nullptr, P, 0, dvariance,
+                          dlengthscales, (double*)dZ);
 }

@@ -457,6 +457,19 @@ int mgp_lowrank_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, cons
 int mgp_lowrank_wide_apply_gated(mgp_handle* h, int dtype, const void* diag_inv, const void* B, int64_t k, int64_t n,
                                  const void* R, int64_t Bt, void* Z, const int* gate);
 
+// kmn_grad.hip, shared with kmn_grad_generic.hip (include/mgp_anyd.h).  mgp_kvjp_check: the argument checks of
+// mgp_kmn_knm_vjp with the largest D the caller serves; zeroes the host outputs, handles N = 0 (*done = 1: nothing is
+// left to do).  mgp_kvjp_fused_d: the D <= MGP_FUSED_MAX_D implementation on checked arguments; panel_rows = 0 is the
+// 256 MiB rule (64 MiB of pack on the fused rank-P form), > 0 that many rows per panel.  mgp_kvjp_symmetrize:
+// G2 = Gq + Gq^T, exactly symmetric.
+int mgp_kvjp_check(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, const void* Z, int64_t M,
+                   const void* Gq, const void* Y, const void* Gb, int32_t P, int max_d, double* dvariance,
+                   double* dlengthscales, void* dZ, int* done);
+int mgp_kvjp_fused_d(mgp_handle* h, const mgp_kernel* k, const double* X, long N, const double* Z, long M,
+                     const double* Gq, const double* Y, const double* Gb, int P, long panel_rows, double* dvariance,
+                     double* dlengthscales, double* dZ);
+int mgp_kvjp_symmetrize(mgp_handle* h, const double* Gq, long M, double* G2);
+
 // Host tail of a kernel-block VJP.  part [nblocks][width] on the device holds per-workgroup sums: width - 1
 // lengthscale sums (the first k->D count), then the variance sum.  They are copied to the host and added in block
 // order (deterministic), then *dvar = tot[width - 1] and dls[d] = variance (-2 / l_d) tot[d].  carry [width], when
