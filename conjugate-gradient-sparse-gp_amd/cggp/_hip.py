@@ -20,6 +20,7 @@ SE, MATERN12, MATERN32, MATERN52 = 0, 1, 2, 3
 COLS, ROWS = 0, 1
 PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK, PRE_LOWRANK, PRE_LOWRANK_WIDE = 0, 1, 2, 3, 4, 5, 6
 OP_DENSE, OP_SGPR, OP_KMM_LAMBDA, OP_KXX_NOISE, OP_KMM_LAMBDA_WIDE = 0, 1, 2, 3, 4
+OP_SGPR_ANYD, OP_KMM_LAMBDA_ANYD, OP_KXX_NOISE_ANYD = 5, 6, 7  # include/mgp_sweep_anyd.h
 
 KERNEL_KINDS = {"se": SE, "matern12": MATERN12, "matern32": MATERN32, "matern52": MATERN52}
 
@@ -172,6 +173,13 @@ ANYD_SIGNATURES = {
                                   ctypes.POINTER(_D), _P]),
 }
 
+# entry points declared in include/mgp_sweep_anyd.h (same library; tests/test_sweep_anyd_abi.py checks this table)
+SWEEP_ANYD_SIGNATURES = {
+    "mgp_knm_matvec_anyd": (_I, [_P, _KP, _P, _L, _P, _L, _P, ctypes.c_int32, _I, _P, _I]),
+    "mgp_kmn_matvec_anyd": (_I, [_P, _KP, _P, _L, _P, _L, _P, ctypes.c_int32, _I, _P, _I]),
+    "mgp_kxx_matvec_anyd": (_I, [_P, _KP, _P, _L, _D, _P, ctypes.c_int32, _I, _P, _I]),
+}
+
 
 def lib_path():
     # MGP_LIBRARY lets A/B measurements load an experimental build; the default is the in-tree one
@@ -191,7 +199,7 @@ def load_library():
                 "(or `make -C conjugate-gradient-sparse-gp_amd/csrc`).  There is no CPU fallback.")
         lib = ctypes.CDLL(path)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
-                                  + list(ANYD_SIGNATURES.items())):
+                                  + list(ANYD_SIGNATURES.items()) + list(SWEEP_ANYD_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -119,16 +119,63 @@ def wide_auto(dtype, D, columns, M):
             and int(M) >= WIDE_MIN_M)
 
 
+# `fused_anyd="auto"` takes the fused any-D sweeps (include/mgp_sweep_anyd.h) for fp64 inputs at
+# FUSED_ANYD_AUTO_MIN_D <= D <= FUSED_ANYD_AUTO_MAX_D[columns]: per measured column count, the largest measured dimension
+# up to which the fused form took at most 0.9 of the panel route's time at every measured point -- both kernels, both
+# orientations, N = 2^18, M = 4096, D in {33, 48, 77, 90, 128, 512} (profiles/sweep_anyd_times.json).  One
+# column: everywhere (0.10 - 0.85).  Eight: up to D = 128 (0.19 - 0.87; 1.14 for K_nm V at D = 512).  Five, which
+# runs as a pass of 4 and a pass of 1 and so forms every distance twice: up to D = 48 (0.21 - 0.84; K_nm V is at 1.17 - 1.24
+# from D = 77 on).  The panel route's time hardly depends on the column count, the fused form's does, so a column count
+# that was not measured is not taken.
+FUSED_ANYD_AUTO_MIN_D = 33
+FUSED_ANYD_AUTO_MAX_D = {1: 512, 5: 48, 8: 128}
+
+
+def check_fused_anyd(fused_anyd, name="fused_anyd"):
+    """`fused_anyd` as given, or `ValueError`: False, True or "auto"."""
+    return check_wide(fused_anyd, name)
+
+
+def fused_anyd_auto(dtype, D, columns=1):
+    """The rule behind `fused_anyd="auto"`: fp64, a measured column count, and
+    FUSED_ANYD_AUTO_MIN_D <= D <= FUSED_ANYD_AUTO_MAX_D[columns]."""
+    return (dtype == torch.float64 and int(columns) in FUSED_ANYD_AUTO_MAX_D
+            and FUSED_ANYD_AUTO_MIN_D <= int(D) <= FUSED_ANYD_AUTO_MAX_D[int(columns)])
+
+
+def use_fused_anyd(fused_anyd, dtype, D, columns=1):
+    """Whether a product or operator with this setting takes the `_anyd` name or kind (which, in fp32 or at D <= 32, is
+    the plain one inside libmgp) for `columns` right-hand sides."""
+    if fused_anyd == "auto":
+        return fused_anyd_auto(dtype, D, columns)
+    return bool(fused_anyd)
+
+
+def anyd_matvec(fused_anyd, which, spec, X, *args, **kwargs):
+    """`ops.knm_matvec`, `ops.kmn_matvec` or `ops.kxx_matvec` (`which` = "knm", "kmn", "kxx"; the arguments after `spec`
+    are theirs), or its `_anyd` form under the rule of `use_fused_anyd`: the one helper the models route their direct
+    products through."""
+    V = args[1]  # (Z, V, ...) or, for kxx, (s2, V, ...)
+    layout = args[2] if len(args) > 2 else kwargs.get("v_layout", kwargs.get("w_layout", ops.COLS))
+    columns = V.shape[1] if layout == ops.COLS else V.shape[0]
+    name = which + "_matvec" + ("_anyd" if use_fused_anyd(fused_anyd, X.dtype, spec.D, columns) else "")
+    return getattr(ops, name)(spec, X, *args, **kwargs)
+
+
 class KmmLambdaOperator(LinearOperator):
     """(k(Z,Z) + diag(lam)) applied matrix-free (row M2, matrix-free alternative).
 
     `wide=False`: libmgp's fused sweep, 8 right-hand sides per launch (`MGP_OP_KMM_LAMBDA`).  `wide=True`: the
     many-column form (`MGP_OP_KMM_LAMBDA_WIDE`: each kernel value evaluated once per 256 right-hand sides and contracted
     on the fp64 matrix cores; fp32 and D > 32 take the sweep form inside libmgp).  `wide="auto"`: the many-column form
-    iff `wide_auto(dtype, D, columns, M)`, decided per solve or product, where the column count is known."""
+    iff `wide_auto(dtype, D, columns, M)`, decided per solve or product, where the column count is known.
 
-    def __init__(self, kernel, Z, lam, wide=False):
+    `fused_anyd` (False, True or "auto"): at D > 32, where `wide` falls back to the sweep, `MGP_OP_KMM_LAMBDA_ANYD` -- the
+    fused any-D sweep instead of kernel panels (fp64; fp32 gives the plain kind's bits).  At D <= 32 `wide` decides."""
+
+    def __init__(self, kernel, Z, lam, wide=False, fused_anyd=False):
         self.wide = check_wide(wide)
+        self.fused_anyd = check_fused_anyd(fused_anyd)
         self.Z = _hip.check_tensor(Z, "Z")
         self.lam = _hip.check_tensor(lam, "lam", dtype=self.Z.dtype).reshape(-1)
         M = self.Z.shape[0]
@@ -142,9 +189,12 @@ class KmmLambdaOperator(LinearOperator):
 
     def kind_for(self, columns):
         """The operator kind libmgp is handed for `columns` right-hand sides."""
+        D = self.Z.shape[1]
+        if D > WIDE_MAX_D and use_fused_anyd(self.fused_anyd, self.dtype, D, max(int(columns), 1)):
+            return _hip.OP_KMM_LAMBDA_ANYD
         wide = self.wide
         if wide == "auto":
-            wide = wide_auto(self.dtype, self.Z.shape[1], columns, self.shape[0])
+            wide = wide_auto(self.dtype, D, columns, self.shape[0])
         return _hip.OP_KMM_LAMBDA_WIDE if wide else _hip.OP_KMM_LAMBDA
 
     def _struct(self):
@@ -168,9 +218,13 @@ class KmmLambdaOperator(LinearOperator):
 
 class KxxNoiseOperator(LinearOperator):
     """(k(X,X) + noise_variance I) applied matrix-free, each unordered pair of rows once (`mgp_kxx_matvec`): the
-    system of exact GP regression, `GPR`'s K + s2 I without the [N,N] matrix.  Single device."""
+    system of exact GP regression, `GPR`'s K + s2 I without the [N,N] matrix.  Single device.
 
-    def __init__(self, kernel, X, noise_variance):
+    `fused_anyd` (False, True or "auto"): `MGP_OP_KXX_NOISE_ANYD` -- at D > 32 in fp64 the fused any-D sweep instead of
+    kernel panels; elsewhere the plain kind's bits."""
+
+    def __init__(self, kernel, X, noise_variance, fused_anyd=False):
+        self.fused_anyd = check_fused_anyd(fused_anyd)
         self.X = _hip.check_tensor(X, "X")
         if self.X.dim() != 2:
             raise ValueError(f"X must be [N, D], got {tuple(self.X.shape)}")
@@ -185,9 +239,13 @@ class KxxNoiseOperator(LinearOperator):
         self.device = self.X.device
 
     def _struct(self):
+        return self._struct_for(1)
+
+    def _struct_for(self, columns):
         k = self.spec.struct(_hip.dtype_code(self.X))
         st = _hip.MgpOperator()
-        st.kind = _hip.OP_KXX_NOISE
+        anyd = use_fused_anyd(self.fused_anyd, self.dtype, self.X.shape[1], max(int(columns), 1))
+        st.kind = _hip.OP_KXX_NOISE_ANYD if anyd else _hip.OP_KXX_NOISE
         st.dtype = k.dtype
         st.n = self.shape[0]
         st.kernel = ctypes.pointer(k)
@@ -207,9 +265,14 @@ class SgprNormalOperator(LinearOperator):
     K_nm is never materialised: each application is two fused N x M sweeps.  With
     `allreduce` set (see `parallel.make_allreduce`) the local [Bt,M] partial K_mn(K_nm p) is
     summed over ranks once per application; Kmm, Z and the CG state are replicated.
+
+    `fused_anyd` (False, True or "auto"): `MGP_OP_SGPR_ANYD` -- at D > 32 in fp64 the two local sweeps run the fused
+    any-D kernel instead of kernel panels (the collective is untouched); elsewhere the plain kind's bits.
     """
 
-    def __init__(self, kernel, X, Z, noise_variance, jitter=0.0, allreduce=None, max_rhs=1, kmm_rows=None):
+    def __init__(self, kernel, X, Z, noise_variance, jitter=0.0, allreduce=None, max_rhs=1, kmm_rows=None,
+                 fused_anyd=False):
+        self.fused_anyd = check_fused_anyd(fused_anyd)
         self.X = _hip.check_tensor(X, "X")
         self.Z = _hip.check_tensor(Z, "Z", dtype=self.X.dtype)
         if self.X.dim() != 2 or self.Z.dim() != 2 or self.X.shape[1] != self.Z.shape[1]:
@@ -273,9 +336,13 @@ class SgprNormalOperator(LinearOperator):
             self._ensure_partial(Bt)
 
     def _struct(self):
+        return self._struct_for(1)
+
+    def _struct_for(self, columns):
         k = self.spec.struct(_hip.dtype_code(self.Z))
         st = _hip.MgpOperator()
-        st.kind = _hip.OP_SGPR
+        anyd = use_fused_anyd(self.fused_anyd, self.dtype, self.Z.shape[1], max(int(columns), 1))
+        st.kind = _hip.OP_SGPR_ANYD if anyd else _hip.OP_SGPR
         st.dtype = k.dtype
         st.n = self.shape[0]
         st.kernel = ctypes.pointer(k)

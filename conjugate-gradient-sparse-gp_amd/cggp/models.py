@@ -15,7 +15,8 @@ import torch
 
 from . import ops
 from .conjugate_gradient import (ConjugateGradient, KmmLambdaOperator, KxxNoiseOperator, PivotedCholeskyPreconditioner,
-                                 SgprNormalOperator, SubsampledNormalPreconditioner, check_wide)
+                                 SgprNormalOperator, SubsampledNormalPreconditioner, anyd_matvec, check_fused_anyd,
+                                 check_wide)
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
 from .slq import slq_log_quadratic
@@ -302,6 +303,11 @@ class CGGP(ClusterGP):
     `W = CG(K_mm + Lambda, K_mn)`, one column per test row), "auto" the many-column form from
     `conjugate_gradient.WIDE_MIN_COLUMNS` columns and `WIDE_MIN_M` inducing points on.
 
+    `fused_anyd` (False, True or "auto"; with `matrix_free=True` only, anything but False without it is a `ValueError`)
+    is the `fused_anyd` argument of every `KmmLambdaOperator` the model makes and the rule of its own K(Z, Z) and
+    K(X*, Z) products: at D > 32 in fp64 libmgp's fused any-D sweeps (include/mgp_sweep_anyd.h) instead of kernel
+    panels; "auto" follows `conjugate_gradient.fused_anyd_auto`.
+
     `data_term` ("batch", the default and the reference's form, or "trace"; fp64 only) is what `elbo(data)` does with
     the rows of `data`.  "batch" solves `W = CG(K_mm + Lambda, K_mn)` with one column per row to sum the diagonal of
     `K_nm W`.  "trace" takes that sum as a trace, `B variance - tr(A^-1 K_mn K_nm)`, and estimates it with the probes
@@ -318,8 +324,12 @@ class CGGP(ClusterGP):
     (`draw_pathwise`).  Value only: `training.TrainableCGGP` is the differentiable form."""
 
     def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, matrix_free=False,
-                 wide_solves=False, data_term="batch", num_bases=1024, num_samples=5, epsilon="matheron", **kwargs):
+                 wide_solves=False, data_term="batch", num_bases=1024, num_samples=5, epsilon="matheron",
+                 fused_anyd=False, **kwargs):
         self.wide_solves = check_wide(wide_solves, "wide_solves")
+        self.fused_anyd = check_fused_anyd(fused_anyd)
+        if self.fused_anyd is not False and not matrix_free:
+            raise ValueError("fused_anyd needs matrix_free=True: without it K_mm is a dense matrix and no sweep runs")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
         super().__init__(kernel, likelihood, inducing_variable, **kwargs)
@@ -340,8 +350,9 @@ class CGGP(ClusterGP):
             return Kmm, KmmLambda, lambda R: ops.symm_matmul(Kmm, R)
         Z = self.inducing_variable.Z
         spec = self.kernel.spec(Z.shape[1])
-        op = KmmLambdaOperator(self.kernel, Z, self.diag_variance[:, 0].contiguous(), wide=self.wide_solves)
-        return None, op, lambda R: ops.knm_matvec(spec, Z, Z, R, ops.ROWS, ops.ROWS)
+        op = KmmLambdaOperator(self.kernel, Z, self.diag_variance[:, 0].contiguous(), wide=self.wide_solves,
+                               fused_anyd=self.fused_anyd)
+        return None, op, lambda R: anyd_matvec(self.fused_anyd, "knm", spec, Z, Z, R, ops.ROWS, ops.ROWS)
 
     def prior_kl(self, probes=None):  # :293-322
         if self.matrix_free and self.num_probes is None and probes is None:
@@ -380,7 +391,7 @@ class CGGP(ClusterGP):
             fvar = (kernel.K_diag(Xnew) - ops.colwise_dot(Kmn, W))[:, None]  # :343-345
         else:
             fvar = (kernel.K(Xnew) - Kmn.t() @ W)[None, ...]  # :347-349
-        fmu = ops.knm_matvec(kernel.spec(Xnew.shape[1]), Xnew, iv.Z, a)  # Kmn^T a, :351 (row M1)
+        fmu = anyd_matvec(self.fused_anyd, "knm", kernel.spec(Xnew.shape[1]), Xnew, iv.Z, a)  # Kmn^T a, :351 (row M1)
         return fmu + self._mean(Xnew), fvar
 
     def predict_f_batched(self, X, batch_size, shared_inverse=False, inverse_threshold=None):
@@ -422,7 +433,7 @@ class CGGP(ClusterGP):
             Knm = ops.k_dense(spec, xb, Z)  # [B, M] = Kmn^T
             Wt = ops.symm_matmul(Y, Knm)  # Kmn^T Y  (Y symmetric)
             variances.append((kernel.K_diag(xb) - (Knm * Wt).sum(dim=1))[:, None])
-            means.append(ops.knm_matvec(spec, xb, Z, a) + self._mean(xb))
+            means.append(anyd_matvec(self.fused_anyd, "knm", spec, xb, Z, a) + self._mean(xb))
         return torch.cat(means, 0), torch.cat(variances, 0)
 
     def _elbo_trace(self, data, probes):
@@ -447,7 +458,7 @@ class CGGP(ClusterGP):
             both = cg(KmmLambda, rhs).diagonal().sum().item()
             if B == 0:
                 return 0.5 * both - 0.5 * (quad - const)
-            fmu = ops.knm_matvec(spec, x, Z, a) + self._mean(x)
+            fmu = anyd_matvec(self.fused_anyd, "knm", spec, x, Z, a) + self._mean(x)
             resid = (y - fmu).contiguous()
             data_sum = -0.5 * B * math.log(2.0 * math.pi * s2) - 0.5 * (ops.dot_all(resid, resid) + B * variance) / s2
             return scale * data_sum + 0.5 * both - 0.5 * (quad - const)
@@ -460,7 +471,8 @@ class CGGP(ClusterGP):
         kl = 0.5 * (quad - trace - const)  # eval_logdet's forward value is 0.0
         if B == 0:
             return -kl
-        out = ops.knm_matvec(spec, x, Z, torch.cat([a, S, probes], dim=1).contiguous())  # [mu | U | V], [B, 2 P + 1]
+        out = anyd_matvec(self.fused_anyd, "knm", spec, x, Z,
+                          torch.cat([a, S, probes], dim=1).contiguous())  # [mu | U | V], [B, 2 P + 1]
         resid = (y - (out[:, :1] + self._mean(x))).contiguous()
         uv = ops.dot_all(out[:, 1:1 + P].contiguous(), out[:, 1 + P:].contiguous()) / P  # ~ tr(A^-1 K_mn K_nm)
         data_sum = -0.5 * B * math.log(2.0 * math.pi * s2) - 0.5 * (ops.dot_all(resid, resid) + B * variance - uv) / s2
@@ -490,7 +502,8 @@ class CGGP(ClusterGP):
         rhs = (self.pseudo_u[:, 0][None, :] - prior[:, B:] - eps).t().contiguous()  # [M, S]
         _, KmmLambda, _ = self._system()
         w = cg(KmmLambda, rhs)
-        f = prior[:, :B] + ops.knm_matvec(kernel.spec(D), x, Z, w.contiguous(), ops.COLS, ops.ROWS)  # [S, B]
+        f = prior[:, :B] + anyd_matvec(self.fused_anyd, "knm", kernel.spec(D), x, Z, w.contiguous(), ops.COLS,
+                                       ops.ROWS)  # [S, B]
         s2 = float(self.likelihood.variance)
         mean = self._mean(x)
         resid = (y.reshape(1, -1) - (f if self.mean_function is None else f + mean.reshape(1, -1))).contiguous()
@@ -648,7 +661,7 @@ class SGPR:
 
     def __init__(self, data, kernel, inducing_variable, noise_variance, conjugate_gradient=None, *,
                  jitter=1e-6, allreduce=None, num_data=None, preconditioner="auto", explicit_rhs=8,
-                 kmm_solver="cholesky"):
+                 kmm_solver="cholesky", fused_anyd=False):
         """`preconditioner`: "auto" (the subsampled normal-equation preconditioner built from
         min(N, 32 M) rows of the data set -- all ranks together), None, or a
         `CGPreconditioner` for the [M,M] system.  `explicit_rhs`: solves on S with at least this
@@ -658,7 +671,11 @@ class SGPR:
         `kmm_solver`: how `K_*m (Kmm+jI)^-1 K_m*` of the predictive variance is formed --
         "cholesky" (GPflow's own `L = chol(Kmm + jitter I)`, one [M,M] factorisation, cached) or
         "cg" (the model's `conjugate_gradient`; Kmm + 1e-6 I is badly conditioned, so this takes
-        hundreds of steps)."""
+        hundreds of steps).
+        `fused_anyd` (False, True or "auto"): handed to the `SgprNormalOperator` and the rule of the model's own
+        K_mn y and K_*m alpha products -- at D > 32 in fp64 libmgp's fused any-D sweeps (include/mgp_sweep_anyd.h)
+        instead of kernel panels; "auto" follows `conjugate_gradient.fused_anyd_auto`."""
+        self.fused_anyd = check_fused_anyd(fused_anyd)
         self.X, self.Y = data
         self.kernel = kernel
         self.inducing_variable = inducingpoint_wrapper(inducing_variable)
@@ -714,7 +731,7 @@ class SGPR:
         if self._op is None:
             self._op = SgprNormalOperator(self.kernel, self.X, self.inducing_variable.Z,
                                           self.likelihood.variance, jitter=self.jitter,
-                                          allreduce=self.allreduce)
+                                          allreduce=self.allreduce, fused_anyd=self.fused_anyd)
         return self._op
 
     def solver(self):
@@ -770,7 +787,7 @@ class SGPR:
 
     def _Kmn_y(self):
         Z = self.inducing_variable.Z
-        b = ops.kmn_matvec(self.kernel.spec(Z.shape[1]), self.X, Z, self.Y)  # K_mn y, [M,1]
+        b = anyd_matvec(self.fused_anyd, "kmn", self.kernel.spec(Z.shape[1]), self.X, Z, self.Y)  # K_mn y, [M,1]
         if self.allreduce is not None:
             self.allreduce(b.view(-1))
         return b
@@ -785,7 +802,7 @@ class SGPR:
         assert not full_output_cov
         self._sync()
         iv, kernel = self.inducing_variable, self.kernel
-        mean = ops.knm_matvec(kernel.spec(Xnew.shape[1]), Xnew, iv.Z, self.alpha())
+        mean = anyd_matvec(self.fused_anyd, "knm", kernel.spec(Xnew.shape[1]), Xnew, iv.Z, self.alpha())
         Kms = Kuf(iv, kernel, Xnew)
         if self.kmm_solver == "cholesky":
             if self._Lmm is None:
@@ -947,12 +964,16 @@ class GPR:
     test row from it (var = K_diag - |k(x*, X) R|^2, an upper bound that tightens with the rank; the mean is
     unchanged).  The cache is dropped with alpha and the operator when the kernel, the noise or the data change.  On
     the Cholesky path the option is ignored: the exact variance is cheaper there.
+    `fused_anyd` (False, True or "auto") is handed to the `KxxNoiseOperator` and is the rule of the model's own
+    k(X*, X) products: at D > 32 in fp64 libmgp's fused any-D sweeps (include/mgp_sweep_anyd.h), not kernel panels.
     `log_marginal_likelihood` needs log|K + s2 I| and exists on the Cholesky path only;
     `log_marginal_likelihood_estimate` is its matrix-free stochastic Lanczos estimate at any N.
     """
 
     def __init__(self, data, kernel, noise_variance=1.0, conjugate_gradient=None, *, solver="auto",
-                 cholesky_max_n=16384, variance_chunk_bytes=256 << 20, variance="solve", variance_rank=128):
+                 cholesky_max_n=16384, variance_chunk_bytes=256 << 20, variance="solve", variance_rank=128,
+                 fused_anyd=False):
+        self.fused_anyd = check_fused_anyd(fused_anyd)
         if solver not in ("auto", "cholesky", "cg"):
             raise ValueError(f"unknown solver {solver!r}")
         if variance not in ("solve", "lanczos"):
@@ -1010,7 +1031,8 @@ class GPR:
         """K + s2 I as a matrix-free operator (`KxxNoiseOperator`)."""
         self._sync()
         if self._op is None:
-            self._op = KxxNoiseOperator(self.kernel, self.data[0], self.likelihood.variance)
+            self._op = KxxNoiseOperator(self.kernel, self.data[0], self.likelihood.variance,
+                                        fused_anyd=self.fused_anyd)
         return self._op
 
     def solve(self, rhs):
@@ -1051,7 +1073,7 @@ class GPR:
                 return mean, cov[None, ...].expand(P, -1, -1).contiguous()
             var = self.kernel.K_diag(Xnew) - (A * A).sum(dim=0)
             return mean, var[:, None].expand(-1, P).contiguous()
-        mean = ops.knm_matvec(spec, Xnew, X, self.alpha())
+        mean = anyd_matvec(self.fused_anyd, "knm", spec, Xnew, X, self.alpha())
         if self.variance == "lanczos":
             cache = self.variance_cache()
             if full_cov:
@@ -1071,7 +1093,8 @@ class GPR:
             Kc = ops.k_dense(spec, X, xs)  # [N, bc]
             Wc = self.conjugate_gradient(self.operator(), Kc)
             if full_cov:
-                cov[:, c0:c0 + step] -= ops.knm_matvec(spec, Xnew, X, Wc)  # K_*X W = K_*X (K + s2 I)^-1 K_X*
+                # K_*X W = K_*X (K + s2 I)^-1 K_X*
+                cov[:, c0:c0 + step] -= anyd_matvec(self.fused_anyd, "knm", spec, Xnew, X, Wc)
             else:
                 var[c0:c0 + step] -= ops.colwise_dot(Kc, Wc)
         if full_cov:

@@ -39,6 +39,16 @@ def _points(t, name, D=None, dtype=None):
 
 def knm_matvec(spec, X, Z, V, v_layout=COLS, out_layout=None):
     """out = k(X, Z) @ V.  V [M,R] (COLS) or [R,M] (ROWS); out [N,R] or [R,N]."""
+    return _knm_matvec("mgp_knm_matvec", spec, X, Z, V, v_layout, out_layout)
+
+
+def knm_matvec_anyd(spec, X, Z, V, v_layout=COLS, out_layout=None):
+    """`knm_matvec` by `mgp_knm_matvec_anyd` (include/mgp_sweep_anyd.h): fp64 at D > 32 the fused any-D sweep on the
+    matrix cores, no kernel panel in memory; fp32 or D <= 32 exactly `knm_matvec`."""
+    return _knm_matvec("mgp_knm_matvec_anyd", spec, X, Z, V, v_layout, out_layout)
+
+
+def _knm_matvec(entry, spec, X, Z, V, v_layout, out_layout):
     X = _points(X, "X", spec.D)
     Z = _points(Z, "Z", spec.D, X.dtype)
     V = _hip.check_tensor(V, "V", dtype=X.dtype)
@@ -56,14 +66,24 @@ def knm_matvec(spec, X, Z, V, v_layout=COLS, out_layout=None):
     # M == 0 (empty inducing set) goes through the C-ABI too: libmgp writes the zeros
     hd = _hip.get_handle(X.device)
     k = spec.struct(_hip.dtype_code(X))
-    hd.check(hd.lib.mgp_knm_matvec(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(V), R,
-                                   v_layout, _hip.ptr(out), out_layout))
+    hd.check(getattr(hd.lib, entry)(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(V), R,
+                                     v_layout, _hip.ptr(out), out_layout))
     return out
 
 
 def kxx_matvec(spec, X, s2, V, v_layout=COLS, out_layout=None):
     """out = (k(X, X) + s2 I) @ V, each unordered pair of rows evaluated once (fp64, D <= 32).
     V [N,R] (COLS) or [R,N] (ROWS); out [N,R] or [R,N]."""
+    return _kxx_matvec("mgp_kxx_matvec", spec, X, s2, V, v_layout, out_layout)
+
+
+def kxx_matvec_anyd(spec, X, s2, V, v_layout=COLS, out_layout=None):
+    """`kxx_matvec` by `mgp_kxx_matvec_anyd`: fp64 at D > 32 the fused any-D sweep of X against itself with s2 V as its
+    addend (every ordered pair); fp32 or D <= 32 exactly `kxx_matvec`."""
+    return _kxx_matvec("mgp_kxx_matvec_anyd", spec, X, s2, V, v_layout, out_layout)
+
+
+def _kxx_matvec(entry, spec, X, s2, V, v_layout, out_layout):
     X = _points(X, "X", spec.D)
     V = _hip.check_tensor(V, "V", dtype=X.dtype)
     if V.dim() != 2:
@@ -81,8 +101,8 @@ def kxx_matvec(spec, X, s2, V, v_layout=COLS, out_layout=None):
         return out
     hd = _hip.get_handle(X.device)
     k = spec.struct(_hip.dtype_code(X))
-    hd.check(hd.lib.mgp_kxx_matvec(hd.h, ctypes.byref(k), _hip.ptr(X), N, s2, _hip.ptr(V), R, v_layout,
-                                   _hip.ptr(out), out_layout))
+    hd.check(getattr(hd.lib, entry)(hd.h, ctypes.byref(k), _hip.ptr(X), N, s2, _hip.ptr(V), R, v_layout,
+                                     _hip.ptr(out), out_layout))
     return out
 
 
@@ -271,6 +291,16 @@ def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e
 
 def kmn_matvec(spec, X, Z, W, w_layout=COLS, out_layout=None):
     """out = k(Z, X) @ W = K_nm^T W.  W [N,R] (COLS) or [R,N] (ROWS); out [M,R] or [R,M]."""
+    return _kmn_matvec("mgp_kmn_matvec", spec, X, Z, W, w_layout, out_layout)
+
+
+def kmn_matvec_anyd(spec, X, Z, W, w_layout=COLS, out_layout=None):
+    """`kmn_matvec` by `mgp_kmn_matvec_anyd`: fp64 at D > 32 the fused any-D sweep, the rows of X cut into chunks whose
+    partials are added in chunk order (bit-reproducible); fp32 or D <= 32 exactly `kmn_matvec`."""
+    return _kmn_matvec("mgp_kmn_matvec_anyd", spec, X, Z, W, w_layout, out_layout)
+
+
+def _kmn_matvec(entry, spec, X, Z, W, w_layout, out_layout):
     X = _points(X, "X", spec.D)
     Z = _points(Z, "Z", spec.D, X.dtype)
     W = _hip.check_tensor(W, "W", dtype=X.dtype)
@@ -287,8 +317,8 @@ def kmn_matvec(spec, X, Z, W, w_layout=COLS, out_layout=None):
     # N == 0 (a rank without rows) goes through the C-ABI too: libmgp writes the zeros
     hd = _hip.get_handle(X.device)
     k = spec.struct(_hip.dtype_code(X))
-    hd.check(hd.lib.mgp_kmn_matvec(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(W), R,
-                                   w_layout, _hip.ptr(out), out_layout))
+    hd.check(getattr(hd.lib, entry)(hd.h, ctypes.byref(k), _hip.ptr(X), N, _hip.ptr(Z), M, _hip.ptr(W), R,
+                                     w_layout, _hip.ptr(out), out_layout))
     return out
 
 

@@ -21,7 +21,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip, ops
-from .conjugate_gradient import ConjugateGradient
+from .conjugate_gradient import ConjugateGradient, anyd_matvec, check_fused_anyd
 from .kernels import Stationary
 from .models import check_data_term, check_pathwise, draw_pathwise, eval_logdet, rademacher
 
@@ -151,12 +151,12 @@ class _KzzTimes(torch.autograd.Function):
     (dvariance, dlengthscales, dZ) by `_kzz_bilinear_grads`."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, Z, V, kind):
+    def forward(ctx, variance, lengthscales, Z, V, kind, fused_anyd=False):
         ctx.spec = ops.KernelSpec(kind, float(variance), [float(x) for x in lengthscales.reshape(-1)], Z.shape[1])
-        ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
+        ctx.v_shape, ctx.l_shape, ctx.fused_anyd = variance.shape, lengthscales.shape, fused_anyd
         V = V.contiguous()
         ctx.save_for_backward(Z, V)
-        return ops.knm_matvec(ctx.spec, Z, Z, V)
+        return anyd_matvec(fused_anyd, "knm", ctx.spec, Z, Z, V)
 
     @staticmethod
     def backward(ctx, G):
@@ -164,8 +164,8 @@ class _KzzTimes(torch.autograd.Function):
         G = G.contiguous()
         dvar, dls, dZ = _kzz_bilinear_grads(ctx.spec, Z, G, V, ctx.needs_input_grad[2])
         gv, gl = _theta_grads(dvar, dls, ctx.v_shape, ctx.l_shape)
-        dV = ops.knm_matvec(ctx.spec, Z, Z, G) if ctx.needs_input_grad[3] else None
-        return gv, gl, dZ, dV, None
+        dV = anyd_matvec(ctx.fused_anyd, "knm", ctx.spec, Z, Z, G) if ctx.needs_input_grad[3] else None
+        return (gv, gl, dZ, dV, None, None)[:len(ctx.needs_input_grad)]  # `fused_anyd` is optional in apply()
 
 
 class _KzzLambdaSolve(torch.autograd.Function):
@@ -175,10 +175,10 @@ class _KzzLambdaSolve(torch.autograd.Function):
     dlam = -sum_r Gb o X; when Z needs a gradient, dZ of the same form by `_kzz_bilinear_grads`."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg, wide=False):
+    def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg, wide=False, fused_anyd=False):
         from .conjugate_gradient import KmmLambdaOperator, _solve_device
         kern = _frozen_kernel(kind, variance, lengthscales)
-        ctx.op = KmmLambdaOperator(kern, Z, lam.detach().contiguous(), wide=wide)
+        ctx.op = KmmLambdaOperator(kern, Z, lam.detach().contiguous(), wide=wide, fused_anyd=fused_anyd)
         ctx.cfg = cg.config(Z.shape[0])
         ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
         rows = rhs.detach().t().contiguous()
@@ -199,8 +199,8 @@ class _KzzLambdaSolve(torch.autograd.Function):
         else:
             dvar, dls = ops.kxx_grad(op.spec, op.Z, Gb, sol, ops.ROWS)
         gv, gl = _theta_grads(-dvar, [-v for v in dls], ctx.v_shape, ctx.l_shape)
-        grads = (gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), dZ, None, None, None)
-        return grads[:len(ctx.needs_input_grad)]  # `wide` is optional in apply()
+        grads = (gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), dZ, None, None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `wide` and `fused_anyd` are optional in apply()
 
 
 class _KzzLambdaLogdet(torch.autograd.Function):
@@ -210,8 +210,8 @@ class _KzzLambdaLogdet(torch.autograd.Function):
     needs a gradient, dZ of the same form by `_kzz_bilinear_grads`."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg, wide=False):
-        ctx.kind, ctx.cg, ctx.have, ctx.wide = kind, cg, solution is not None, wide
+    def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg, wide=False, fused_anyd=False):
+        ctx.kind, ctx.cg, ctx.have, ctx.wide, ctx.fused_anyd = kind, cg, solution is not None, wide, fused_anyd
         ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
         ctx.theta = (float(variance), lengthscales.detach().clone())
         ctx.save_for_backward(lam.detach(), probes, Z, *((solution,) if ctx.have else ()))
@@ -226,15 +226,16 @@ class _KzzLambdaLogdet(torch.autograd.Function):
             S = ctx.saved_tensors[3]
         else:
             with torch.no_grad():
-                S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous(), wide=ctx.wide), probes)
+                S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous(), wide=ctx.wide, fused_anyd=ctx.fused_anyd),
+                           probes)
         P = probes.shape[1]
         scale = float(df) / P
         dvar, dls, dZ = _kzz_bilinear_grads(kern.spec(Z.shape[1]), Z, S.contiguous(), probes.contiguous(),
                                             ctx.needs_input_grad[5])
         gv, gl = _theta_grads(scale * dvar, [scale * v for v in dls], ctx.v_shape, ctx.l_shape)
         grads = (gv, gl, scale * (S * probes).sum(dim=1), None, None, None if dZ is None else scale * dZ, None, None,
-                 None)
-        return grads[:len(ctx.needs_input_grad)]  # `wide` is optional in apply()
+                 None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `wide` and `fused_anyd` are optional in apply()
 
 
 PANEL_BYTES = 256 << 20  # the largest row panel of a [B, M] cotangent that `_knm_theta_grads_panels` forms
@@ -262,13 +263,14 @@ class _KnmTimes(torch.autograd.Function):
     by `_knm_theta_grads_panels`; a Z that needs a gradient there is refused at the model's construction."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, Z, V, C, x, kind):
+    def forward(ctx, variance, lengthscales, Z, V, C, x, kind, fused_anyd=False):
         ctx.spec = ops.KernelSpec(kind, float(variance), [float(v) for v in lengthscales.reshape(-1)], Z.shape[1])
         ctx.v_shape, ctx.l_shape, ctx.live = variance.shape, lengthscales.shape, V.shape[1]
+        ctx.fused_anyd = fused_anyd
         VC = torch.cat([V.detach(), C.detach()], dim=1).contiguous()
         Zd = Z.detach()
         ctx.save_for_backward(Zd, VC, x)
-        return ops.knm_matvec(ctx.spec, x, Zd, VC)
+        return anyd_matvec(fused_anyd, "knm", ctx.spec, x, Zd, VC)
 
     @staticmethod
     def backward(ctx, G):
@@ -285,8 +287,8 @@ class _KnmTimes(torch.autograd.Function):
         gv, gl = _theta_grads(dvar, dls, ctx.v_shape, ctx.l_shape)
         dV = None
         if ctx.needs_input_grad[3]:
-            dV = ops.kmn_matvec(spec, x, Zd, G[:, :ctx.live].contiguous())
-        return gv, gl, dZ, dV, None, None, None
+            dV = anyd_matvec(ctx.fused_anyd, "kmn", spec, x, Zd, G[:, :ctx.live].contiguous())
+        return (gv, gl, dZ, dV, None, None, None, None)[:len(ctx.needs_input_grad)]  # `fused_anyd` is optional
 
 
 def _rff_vjp_panels(x, theta, W, scale, G, want_dX=False):
@@ -386,6 +388,9 @@ class TrainableCGGP:
     whose backward passes contract dL/dK with dK/dtheta by `mgp_kxx_grad`; the [M, B] block of a batch keeps `_KBlock`.
     The exact trace (`num_probes=None` without `probes`) needs M right-hand sides and raises `ValueError`.
     `fused_solves=True` works there too: one operator solve on the columns [pseudo_u, K_mn, probes].
+    `fused_anyd` (False, True or "auto"; with `matrix_free=True` only) is handed to every `KmmLambdaOperator` and is
+    the rule of the K(Z, Z) and K(x, Z) products of the autograd nodes (forward and the `dV` of their backward), as in
+    `models.CGGP`; the hyper-parameter gradients keep their entry points.
     `wide_solves` (False, True or "auto"; with `matrix_free=True` only) is handed to every `KmmLambdaOperator`, as in
     `models.CGGP`.
 
@@ -437,11 +442,14 @@ class TrainableCGGP:
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
                  num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
                  wide_solves=False, trainable_inducing=False, data_term="batch", num_bases=1024, num_samples=5,
-                 epsilon="matheron"):
+                 epsilon="matheron", fused_anyd=False):
         from .conjugate_gradient import check_wide
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
+        self.fused_anyd = check_fused_anyd(fused_anyd)
+        if self.fused_anyd is not False and not matrix_free:
+            raise ValueError("fused_anyd needs matrix_free=True: without it K_mm is a dense matrix and no sweep runs")
         self.data_term = check_data_term(data_term, Z.dtype, Z.shape[1], trainable_inducing)
         self.num_bases, self.num_samples, self.epsilon = check_pathwise(num_bases, num_samples, epsilon)
         self.pathwise_seed = 0
@@ -490,9 +498,9 @@ class TrainableCGGP:
             probes = rademacher((M, self.num_probes), dt, dev, self.probe_seed)
             self.probe_seed += 1
         P = probes.shape[1]
-        times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind)
+        times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
         wide = self.wide_solves
-        solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide)
+        solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
         if self.fused_solves:
             B = Kmn.shape[1]
             sol = solve(torch.cat([self.pseudo_u, Kmn, probes], dim=1))  # :303, :339, :311 in one solve
@@ -507,9 +515,11 @@ class TrainableCGGP:
         if self.independent_logdet_probes:
             own = rademacher((M, P), dt, dev, self.logdet_probe_seed)  # fresh draw, :38-39
             self.logdet_probe_seed += 1
-            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None, own, Z, kind, cg, wide)  # solved in the backward pass
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None, own, Z, kind, cg, wide,
+                                            self.fused_anyd)  # solved in the backward pass
         else:
-            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, S.detach(), probes, Z, kind, cg, wide)  # K^-1 Zp reused
+            logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, S.detach(), probes, Z, kind, cg, wide,
+                                            self.fused_anyd)  # K^-1 Zp reused
         const = torch.log(lam).sum()  # :321
         kl = 0.5 * (quad - trace + logdet - const)
         scale = 1.0 if self.num_data is None else float(self.num_data) / float(x.shape[0])  # :163-169
@@ -545,7 +555,8 @@ class TrainableCGGP:
             self.logdet_probe_seed += 1
         if self.matrix_free:  # solved in the backward pass from `own`, else K^-1 Zp reused
             logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None if own is not None else S.detach(),
-                                            probes if own is None else own, Z, kind, cg, self.wide_solves)
+                                            probes if own is None else own, Z, kind, cg, self.wide_solves,
+                                            self.fused_anyd)
         elif own is not None:
             logdet = eval_logdet(KL, cg, P, own)  # second probe solve in the backward pass, :40-42
         else:
@@ -569,14 +580,14 @@ class TrainableCGGP:
         lam = s2 / self.cluster_counts[:, 0]  # diag_variance, :226-228
         if self.matrix_free:
             wide = self.wide_solves
-            times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind)
-            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide)
+            times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
+            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
         else:
             Kmm = self.kernel.K(Z)  # :300 / :333
             KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
             times_kzz = lambda V: Kmm @ V
             solve = lambda rhs: cg(KL, rhs)
-        knm_times = lambda V, C: _KnmTimes.apply(var_p, ls, Z, V, C, x.contiguous(), kind)
+        knm_times = lambda V, C: _KnmTimes.apply(var_p, ls, Z, V, C, x.contiguous(), kind, self.fused_anyd)
         scale = 1.0 if self.num_data is None or B == 0 else float(self.num_data) / float(B)  # :163-169
         const = torch.log(lam).sum()  # :321
         log_norm = -0.5 * B * (math.log(2.0 * math.pi) + torch.log(s2))
@@ -629,8 +640,8 @@ class TrainableCGGP:
         KL = None
         if self.matrix_free:
             wide = self.wide_solves
-            times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind)
-            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide)
+            times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
+            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
         else:
             Kmm = self.kernel.K(Z)  # :300 / :333
             KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
@@ -652,7 +663,8 @@ class TrainableCGGP:
             kl, _, _, _, w = self._probed_kl(probes, solve, times_kzz, KL, lam, var_p, ls, extra=rhs)
         if B == 0:
             return -kl
-        corr = _KnmTimes.apply(var_p, ls, Z, w, w.new_empty((M, 0)), x.contiguous(), kind)  # [B, S], :418
+        corr = _KnmTimes.apply(var_p, ls, Z, w, w.new_empty((M, 0)), x.contiguous(), kind,
+                               self.fused_anyd)  # [B, S], :418
         f = prior[:, :B] + corr.t()  # :419
         sq = ((y.reshape(1, -1) - f) ** 2).sum()  # :384-385
         scale = 1.0 if self.num_data is None else float(self.num_data) / float(B)  # :163-169
@@ -727,7 +739,7 @@ class TrainableCGGP:
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
                     num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves,
                     data_term=self.data_term, num_bases=self.num_bases, num_samples=self.num_samples,
-                    epsilon=self.epsilon)
+                    epsilon=self.epsilon, fused_anyd=self.fused_anyd)
 
 
 class _GPRLmlEstimate(torch.autograd.Function):
@@ -746,13 +758,13 @@ class _GPRLmlEstimate(torch.autograd.Function):
     unbiased because E[z z^T] = P whatever P is."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, s2, X, Y, probes, kind, cg, num_probes=None, seed=0):
+    def forward(ctx, variance, lengthscales, s2, X, Y, probes, kind, cg, num_probes=None, seed=0, fused_anyd=False):
         from . import kernels
         from .models import GPR
         cls = {"se": kernels.SquaredExponential, "matern12": kernels.Matern12, "matern32": kernels.Matern32,
                "matern52": kernels.Matern52}[kind]
         kern = cls(variance=float(variance), lengthscales=[float(v) for v in lengthscales.reshape(-1)])
-        model = GPR((X, Y), kern, noise_variance=float(s2), conjugate_gradient=cg, solver="cg")
+        model = GPR((X, Y), kern, noise_variance=float(s2), conjugate_gradient=cg, solver="cg", fused_anyd=fused_anyd)
         if probes is None:
             est, alpha, W, Z = model._lml_estimate(num_probes=num_probes, seed=seed)
         else:
@@ -772,8 +784,9 @@ class _GPRLmlEstimate(torch.autograd.Function):
         ds2 = float((U * V).sum())
         n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
         gl = torch.tensor(dls if n_l > 1 else [sum(dls)], dtype=torch.float64).reshape(ctx.l_shape)
-        return (g * torch.tensor(dvar, dtype=torch.float64), g * gl, g * torch.tensor(ds2, dtype=torch.float64),
-                None, None, None, None, None, None, None)
+        grads = (g * torch.tensor(dvar, dtype=torch.float64), g * gl, g * torch.tensor(ds2, dtype=torch.float64),
+                 None, None, None, None, None, None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `num_probes`, `seed` and `fused_anyd` are optional in apply()
 
 
 class TrainableGPR:
@@ -791,9 +804,14 @@ class TrainableGPR:
     of `probe_seed`; a probe set assigned to `self.probes` by the caller is then taken as draws with E[z z^T] = P.
     The gradient comes from one `mgp_kxx_grad` call (`_GPRLmlEstimate`).  It is
     an unbiased estimate of the true gradient, NOT the exact derivative of the fixed-probe value, so an L-BFGS line
-    search may see the two disagree: Adam is the tested optimiser here."""
+    search may see the two disagree: Adam is the tested optimiser here.
 
-    def __init__(self, kernel, noise_variance, X, Y, *, num_probes=None, probe_seed=0, conjugate_gradient=None):
+    `fused_anyd` (False, True or "auto"): the setting of the matrix-free estimate's `KxxNoiseOperator` and of the
+    frozen model, as on `models.GPR`; the gradient call (`mgp_kxx_grad`) is not affected."""
+
+    def __init__(self, kernel, noise_variance, X, Y, *, num_probes=None, probe_seed=0, conjugate_gradient=None,
+                 fused_anyd=False):
+        self.fused_anyd = check_fused_anyd(fused_anyd)  # the matrix-free estimate's operator and the frozen model's
         self.kernel = TrainableKernel(kernel)
         self.likelihood_variance = Parameter(noise_variance)
         self.X, self.Y = X, Y
@@ -837,7 +855,8 @@ class TrainableGPR:
             if ls.dim() == 0:
                 ls = ls.reshape(1)
             return _GPRLmlEstimate.apply(self.kernel.variance_p(), ls, s2, X.contiguous(), Y.contiguous(), None,
-                                         self.kernel.name, self.conjugate_gradient, self.num_probes, self.probe_seed)
+                                         self.kernel.name, self.conjugate_gradient, self.num_probes, self.probe_seed,
+                                         self.fused_anyd)
         if self.num_probes is not None:
             probes = self.probes if self.probes.shape[0] == N else None
             if probes is None:  # another row count than the model's own data: a draw of that size
@@ -848,7 +867,7 @@ class TrainableGPR:
             if ls.dim() == 0:
                 ls = ls.reshape(1)
             return _GPRLmlEstimate.apply(self.kernel.variance_p(), ls, s2, X.contiguous(), Y.contiguous(), probes,
-                                         self.kernel.name, self.conjugate_gradient)
+                                         self.kernel.name, self.conjugate_gradient, None, 0, self.fused_anyd)
         K = self.kernel.K(X) + s2.to(X.device) * torch.eye(N, dtype=X.dtype, device=X.device)
         L = torch.linalg.cholesky(K)
         v = torch.linalg.solve_triangular(L, Y, upper=False)
@@ -866,9 +885,10 @@ class TrainableGPR:
             raise TypeError(f"frozen_model() got unexpected keyword arguments {sorted(unknown)}")
         if self.num_probes is not None:
             return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
-                       conjugate_gradient=self.conjugate_gradient, solver="cg", **gpr_kwargs)
+                       conjugate_gradient=self.conjugate_gradient, solver="cg", fused_anyd=self.fused_anyd,
+                       **gpr_kwargs)
         return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
-                   solver="cholesky", **gpr_kwargs)
+                   solver="cholesky", fused_anyd=self.fused_anyd, **gpr_kwargs)
 
 
 def sgpr_bound(Kmm_j, Q, b, yy, s2, variance, N):
@@ -972,7 +992,7 @@ class _SGPRElbo(torch.autograd.Function):
         spec = ops.KernelSpec(model.kernel.name, float(variance), [float(v) for v in lengthscales.reshape(-1)], D)
         Zd = Z.detach()
         Q = ops.kmn_knm(spec, X, Zd)
-        b = ops.kmn_matvec(spec, X, Zd, Y)
+        b = anyd_matvec(model.fused_anyd, "kmn", spec, X, Zd, Y)
         yy = ops.dot_all(Y, Y)
         if model.allreduce is not None:
             model.allreduce(Q.view(-1))
@@ -1029,13 +1049,16 @@ class TrainableSGPR:
     `models.SGPR`: X, Y are this rank's rows) the forward sums Q, K_mn y and y^T y over ranks and the backward makes one
     all-reduce of its N-sized partials, so every rank ends with the same gradient.  fp64, Y [N, 1]; any D <= 512: above
     D = 32 the N-sized part is `mgp_kmn_knm_vjp_anyd`, whose kernels stage the dimensions through LDS, and the
-    constructor refuses X, Y, Z that are not on the GPU (ValueError)."""
+    constructor refuses X, Y, Z that are not on the GPU (ValueError).  `fused_anyd` (False, True or "auto"): the rule
+    of the bound's `K_mn y` product and the setting of the frozen model, as on `models.SGPR`; `mgp_kmn_knm` and the VJP
+    are not affected."""
 
     num_probes = None
     internal_data = True
 
     def __init__(self, kernel, noise_variance, X, Y, Z, *, jitter=1e-6, trainable_inducing=False, allreduce=None,
-                 num_data=None, conjugate_gradient=None):
+                 num_data=None, conjugate_gradient=None, fused_anyd=False):
+        self.fused_anyd = check_fused_anyd(fused_anyd)  # K_mn y of the bound, and the frozen model's sweeps
         for name, t in (("X", X), ("Y", Y), ("Z", Z)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
                 raise ValueError(f"TrainableSGPR needs fp64 tensors: {name} is "
@@ -1084,7 +1107,8 @@ class TrainableSGPR:
     def frozen_model(self):
         from .models import SGPR
         return SGPR((self.X, self.Y), self.kernel.frozen(), self.Z.detach().clone(), self.noise_p.value,
-                    self.conjugate_gradient, jitter=self.jitter, allreduce=self.allreduce, num_data=self.num_data)
+                    self.conjugate_gradient, jitter=self.jitter, allreduce=self.allreduce, num_data=self.num_data,
+                    fused_anyd=self.fused_anyd)
 
 
 def train_using_adam_and_update(data, model, iterations, batch_size, learning_rate, update_fn=None,

@@ -101,7 +101,15 @@ extern "C" int mgp_create(mgp_handle** out, int device) {
     delete h;
     return MGP_E_NOMEM;
   }
+  if (hipMalloc((void**)&h->anyd_sc, MGP_MAX_D * sizeof(double)) != hipSuccess) {
+    (void)hipFree(h->dparams);
+    (void)hipFree(h->ones);
+    (void)hipHostFree(h->host_flag);
+    delete h;
+    return MGP_E_NOMEM;
+  }
   if (mgp_build_e2tabs(h) != MGP_OK) {
+    (void)hipFree(h->anyd_sc);
     (void)hipFree(h->dparams);
     (void)hipFree(h->ones);
     (void)hipHostFree(h->host_flag);
@@ -172,6 +180,7 @@ extern "C" int mgp_destroy(mgp_handle* h) {
   if (h->aside_stream) (void)hipStreamDestroy(h->aside_stream);
   if (h->ones) (void)hipFree(h->ones);
   if (h->dparams) (void)hipFree(h->dparams);
+  if (h->anyd_sc) (void)hipFree(h->anyd_sc);
   if (h->e2tabs) (void)hipFree(h->e2tabs);
   for (auto& pr : h->prof_ev) {
     (void)hipEventDestroy(pr.first);

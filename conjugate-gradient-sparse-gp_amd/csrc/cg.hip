@@ -22,6 +22,7 @@
 #include <chrono>
 #include <cstdio>
 
+#include "../../include/mgp_sweep_anyd.h"
 #include "mgp_common.h"
 
 namespace {
@@ -417,9 +418,11 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
       if (mgp_kmm_wide_serves(op->kernel))
         return mgp_kmm_wide_apply(h, op->kernel, op->Z, op->M, op->lambda, P, Bt, out, gate);
       [[fallthrough]];
+    case MGP_OP_KMM_LAMBDA_ANYD:  // the fused any-D sweep where it serves (sweep_anyd.hip), else the code below
     case MGP_OP_KMM_LAMBDA: {
-      MGP_TRY(mgp_sweep(h, op->kernel, op->Z, op->M, op->Z, op->M, VecView{P, 1, n}, (int)Bt,
-                        VecViewMut{out, 1, n}, 0.0, VecView{nullptr, 0, 0}, gate));
+      MGP_TRY((op->kind == MGP_OP_KMM_LAMBDA_ANYD ? mgp_sweep_anyd : mgp_sweep)(
+          h, op->kernel, op->Z, op->M, op->Z, op->M, VecView{P, 1, n}, (int)Bt, VecViewMut{out, 1, n}, 0.0,
+          VecView{nullptr, 0, 0}, gate));
       hipLaunchKernelGGL((add_diag_prod_kernel<T>), dim3(nblk(Bt * n)), dim3(256), 0, h->stream, gate,
                          (const T*)op->lambda, P, out, n, Bt * n);
       MGP_LAUNCH_CHECK(h);
@@ -427,7 +430,11 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
     }
     case MGP_OP_KXX_NOISE:  // (k(X,X) + s2 I) p, each unordered pair once (kxx.hip); rows of P are the right-hand sides
       return mgp_kxx(h, op->kernel, op->X, n, op->s2, VecView{P, 1, n}, (int)Bt, VecViewMut{out, 1, n}, gate);
+    case MGP_OP_KXX_NOISE_ANYD:
+      return mgp_kxx_anyd(h, op->kernel, op->X, n, op->s2, VecView{P, 1, n}, (int)Bt, VecViewMut{out, 1, n}, gate);
+    case MGP_OP_SGPR_ANYD:  // the two local sweeps by the fused any-D kernel where it serves; everything else as below
     case MGP_OP_SGPR: {
+      const auto sweep = op->kind == MGP_OP_SGPR_ANYD ? mgp_sweep_anyd : mgp_sweep;
       // u[Bt,N] = (K_nm p^T)^T ; t[Bt,M] = (K_mn u^T)^T over the local rows ; the replicated
       // s2*Kmm.p term is added as this rank's row slab of it, so ONE all-reduce of t finishes S.p
       const long N = op->N, M = op->M;
@@ -469,15 +476,15 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
         h->stream = main_stream;
         MGP_TRY(rc);
         MGP_HIP(h, hipEventRecord(h->aside_ev[1], h->aside_stream));
-        MGP_TRY(mgp_sweep(h, op->kernel, op->X, N, op->Z, M, VecView{P, 1, M}, (int)Bt, VecViewMut{u, 1, N}, 0.0,
+        MGP_TRY(sweep(h, op->kernel, op->X, N, op->Z, M, VecView{P, 1, M}, (int)Bt, VecViewMut{u, 1, N}, 0.0,
                           VecView{nullptr, 0, 0}, gate));
         MGP_HIP(h, hipStreamWaitEvent(main_stream, h->aside_ev[1], 0));
-        MGP_TRY(mgp_sweep(h, op->kernel, op->Z, M, op->X, N, VecView{u, 1, N}, (int)Bt, VecViewMut{tt, 1, M}, op->s2,
+        MGP_TRY(sweep(h, op->kernel, op->Z, M, op->X, N, VecView{u, 1, N}, (int)Bt, VecViewMut{tt, 1, M}, op->s2,
                           VecView{kmp, 1, M}, gate));
       } else if (N > 0) {
-        MGP_TRY(mgp_sweep(h, op->kernel, op->X, N, op->Z, M, VecView{P, 1, M}, (int)Bt, VecViewMut{u, 1, N}, 0.0,
+        MGP_TRY(sweep(h, op->kernel, op->X, N, op->Z, M, VecView{P, 1, M}, (int)Bt, VecViewMut{u, 1, N}, 0.0,
                           VecView{nullptr, 0, 0}, gate));
-        MGP_TRY(mgp_sweep(h, op->kernel, op->Z, M, op->X, N, VecView{u, 1, N}, (int)Bt, VecViewMut{tt, 1, M}, 0.0,
+        MGP_TRY(sweep(h, op->kernel, op->Z, M, op->X, N, VecView{u, 1, N}, (int)Bt, VecViewMut{tt, 1, M}, 0.0,
                           VecView{nullptr, 0, 0}, gate));
       } else {
         MGP_HIP(h, hipMemsetAsync(tt, 0, (size_t)Bt * M * sizeof(T), h->stream));
@@ -529,20 +536,22 @@ int check_operator(mgp_handle* h, const mgp_operator* op) {
   if (!op) return mgp_fail(h, MGP_E_BADARG, "operator is NULL");
   if (op->dtype != MGP_F32 && op->dtype != MGP_F64) return mgp_fail(h, MGP_E_DTYPE, "bad operator dtype");
   if (op->n <= 0) return mgp_fail(h, MGP_E_SHAPE, "operator n must be > 0");
+  const bool sgpr = op->kind == MGP_OP_SGPR || op->kind == MGP_OP_SGPR_ANYD;
   if (op->kind == MGP_OP_DENSE) {
     if (!op->A) return mgp_fail(h, MGP_E_BADARG, "dense operator without matrix");
-  } else if (op->kind == MGP_OP_SGPR || op->kind == MGP_OP_KMM_LAMBDA || op->kind == MGP_OP_KMM_LAMBDA_WIDE) {
+  } else if (sgpr || op->kind == MGP_OP_KMM_LAMBDA || op->kind == MGP_OP_KMM_LAMBDA_WIDE ||
+             op->kind == MGP_OP_KMM_LAMBDA_ANYD) {
     MGP_TRY(mgp_check_kernel(h, op->kernel));
     if (op->kernel->dtype != op->dtype) return mgp_fail(h, MGP_E_DTYPE, "operator/kernel dtype mismatch");
     if (op->M != op->n || !op->Z) return mgp_fail(h, MGP_E_SHAPE, "operator needs Z with M == n");
-    if (op->kind == MGP_OP_SGPR && (!op->Kmm || op->N < 0 || (op->N > 0 && !op->X)))
+    if (sgpr && (!op->Kmm || op->N < 0 || (op->N > 0 && !op->X)))
       return mgp_fail(h, MGP_E_BADARG, "SGPR operator needs X and Kmm");
-    if (op->kind != MGP_OP_SGPR && !op->lambda) return mgp_fail(h, MGP_E_BADARG, "needs lambda");
-    if (op->kind == MGP_OP_SGPR && op->allreduce && op->comm)
+    if (!sgpr && !op->lambda) return mgp_fail(h, MGP_E_BADARG, "needs lambda");
+    if (sgpr && op->allreduce && op->comm)
       return mgp_fail(h, MGP_E_BADARG, "give either the allreduce hook or a communicator, not both");
-    if (op->kind == MGP_OP_SGPR && op->allreduce && op->world_size < 1)
+    if (sgpr && op->allreduce && op->world_size < 1)
       return mgp_fail(h, MGP_E_BADARG, "allreduce hook needs world_size >= 1");
-  } else if (op->kind == MGP_OP_KXX_NOISE) {
+  } else if (op->kind == MGP_OP_KXX_NOISE || op->kind == MGP_OP_KXX_NOISE_ANYD) {
     MGP_TRY(mgp_check_kernel(h, op->kernel));
     if (op->kernel->dtype != op->dtype) return mgp_fail(h, MGP_E_DTYPE, "operator/kernel dtype mismatch");
     if (op->N != op->n || !op->X) return mgp_fail(h, MGP_E_SHAPE, "K_XX operator needs X with N == n");
@@ -718,7 +727,9 @@ struct CgSolve {
     const bool fuse = fused && !reset;
     // only the fused update can read A.p from somewhere else: the skinny product's slices (dense operator) or the
     // all-reduced partial of the collective SGPR operator, each where its durable switch allows
-    const bool may_defer = fuse && ((op->kind == MGP_OP_DENSE && h->skinny_defer) || (op->kind == MGP_OP_SGPR && h->fuse_agree));
+    // (MGP_OP_SGPR_ANYD defers as MGP_OP_SGPR does: the deferral concerns the collective, not the two local sweeps)
+    const bool sgpr = op->kind == MGP_OP_SGPR || op->kind == MGP_OP_SGPR_ANYD;
+    const bool may_defer = fuse && ((op->kind == MGP_OP_DENSE && h->skinny_defer) || (sgpr && h->fuse_agree));
     MgpApLoc ap{a.ap, 1, 0, nullptr, 0};
     MGP_TRY(apply_operator<T>(h, op, a.p, Bt, a.ap, gate, may_defer ? &ap : nullptr));
     if (fuse) return fused_update(ap);

@@ -89,6 +89,10 @@ struct mgp_handle {
   void* ones = nullptr;  // device constants: double 1.0 at +0, float 1.0f at +8
   void* e2tabs = nullptr;  // exp2 tables of the fast fp64 sweep (8192 + 2048 entries, sweep.hip: mgp_build_e2tabs)
   double* dparams = nullptr;  // device copy of c/lengthscale_d for the generic-D kernels [MGP_MAX_D]
+  // the same for the fused any-D sweeps (sweep_anyd.hip), with the host copy of what stands there: uploaded on change
+  double* anyd_sc = nullptr;
+  double anyd_sc_host[MGP_MAX_D] = {0};
+  int anyd_sc_n = 0;  // entries of anyd_sc that are valid (0: none)
   int num_cus = 256;
   // 0 = fused sweeps on the VALU (sweep.hip, default: measured faster), 1 = fp64 distance
   // cross-term on the matrix cores (sweep_mfma.hip); MGP_SWEEP=mfma selects 1 for A/B runs
@@ -436,6 +440,16 @@ int mgp_kmn_sq_colsum_generic(mgp_handle* h, const mgp_kernel* k, const void* X,
                               void* out);
 int mgp_gemm_nt(mgp_handle* h, int dtype, const void* P, int64_t ldp, int64_t m, const void* A, int64_t lda, int64_t n,
                 int64_t K, void* out, int64_t ldo, int accumulate, const int* gate);
+// sweep_anyd.hip (include/mgp_sweep_anyd.h): mgp_sweep's contract on the matrix cores with K in slices, fp64 and
+// D > MGP_FUSED_MAX_D (mgp_sweep_anyd_serves); mgp_sweep_anyd / mgp_kxx_anyd take it where it serves and are mgp_sweep /
+// mgp_kxx otherwise
+bool mgp_sweep_anyd_serves(const mgp_kernel* k);
+int mgp_sweep_fused_anyd(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
+                         VecView W, int32_t R, VecViewMut out, double alpha, VecView addend, const int* gate);
+int mgp_sweep_anyd(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb, VecView W,
+                   int32_t R, VecViewMut out, double alpha, VecView addend, const int* gate);
+int mgp_kxx_anyd(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, VecView V, int32_t R,
+                 VecViewMut out, const int* gate);
 int mgp_sweep_mfma_f64(mgp_handle* h, const mgp_kernel* k, const double* A, long na, const double* B, long nb,
                        const double* W, long w_sj, long w_sr, int R, double* out, long o_si, long o_sr,
                        double alpha, const double* addend, long ad_si, long ad_sr, const int* gate);
