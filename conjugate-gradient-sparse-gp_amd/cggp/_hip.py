@@ -180,6 +180,11 @@ SWEEP_ANYD_SIGNATURES = {
     "mgp_kxx_matvec_anyd": (_I, [_P, _KP, _P, _L, _D, _P, ctypes.c_int32, _I, _P, _I]),
 }
 
+# entry points declared in include/mgp_predict.h (same library; tests/test_predict_abi.py checks this table)
+PREDICT_SIGNATURES = {
+    "mgp_knm_quadform": (_I, [_P, _KP, _P, _L, _P, _L, _P, _L, _P]),
+}
+
 
 def lib_path():
     # MGP_LIBRARY lets A/B measurements load an experimental build; the default is the in-tree one
@@ -199,7 +204,8 @@ def load_library():
                 "(or `make -C conjugate-gradient-sparse-gp_amd/csrc`).  There is no CPU fallback.")
         lib = ctypes.CDLL(path)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
-                                  + list(ANYD_SIGNATURES.items()) + list(SWEEP_ANYD_SIGNATURES.items())):
+                                  + list(ANYD_SIGNATURES.items()) + list(SWEEP_ANYD_SIGNATURES.items())
+                                  + list(PREDICT_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

@@ -151,6 +151,34 @@ def use_fused_anyd(fused_anyd, dtype, D, columns=1):
     return bool(fused_anyd)
 
 
+# `fused_variance="auto"` takes `ops.knm_quadform` (include/mgp_predict.h) for the whole-test-set variance k C k of
+# SGPR and CDGP where the fused kernel took at most 0.9 of the time of the composition (`ops.k_dense` + `ops.symm_matmul`
+# + row sum) at every measured point: fp64, D <= 32 and M >= FUSED_VARIANCE_AUTO_MIN_M, both measured kernels, B = 2^16
+# (profiles/predict_quadform_times.json).  None: no such region exists and "auto" means False -- measured,
+# fused / composition: 0.98, 1.09, 1.09 at M = 1024, 4096, 8192 for SE at D = 8 and 1.68, 1.96, 1.98 for Matern-3/2 at D = 32.
+FUSED_VARIANCE_AUTO_MIN_M = None
+FUSED_VARIANCE_MAX_D = 32  # MGP_FUSED_MAX_D: above it, and in fp32, libmgp runs the composition itself
+
+
+def check_fused_variance(fused_variance, name="fused_variance"):
+    """`fused_variance` as given, or `ValueError`: False, True or "auto"."""
+    return check_wide(fused_variance, name)
+
+
+def fused_variance_auto(dtype, D, M):
+    """The rule behind `fused_variance="auto"`."""
+    return (FUSED_VARIANCE_AUTO_MIN_M is not None and dtype == torch.float64 and int(D) <= FUSED_VARIANCE_MAX_D
+            and int(M) >= FUSED_VARIANCE_AUTO_MIN_M)
+
+
+def use_fused_variance(fused_variance, dtype, D, M):
+    """Whether a whole-test-set variance with this setting calls `ops.knm_quadform` (True: always) or composes the
+    form from `ops.k_dense`, `ops.symm_matmul` and a row sum."""
+    if fused_variance == "auto":
+        return fused_variance_auto(dtype, D, M)
+    return bool(fused_variance)
+
+
 def anyd_matvec(fused_anyd, which, spec, X, *args, **kwargs):
     """`ops.knm_matvec`, `ops.kmn_matvec` or `ops.kxx_matvec` (`which` = "knm", "kmn", "kxx"; the arguments after `spec`
     are theirs), or its `_anyd` form under the rule of `use_fused_anyd`: the one helper the models route their direct

@@ -16,7 +16,7 @@ import torch
 from . import ops
 from .conjugate_gradient import (ConjugateGradient, KmmLambdaOperator, KxxNoiseOperator, PivotedCholeskyPreconditioner,
                                  SgprNormalOperator, SubsampledNormalPreconditioner, anyd_matvec, check_fused_anyd,
-                                 check_wide)
+                                 check_fused_variance, check_wide, use_fused_variance)
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
 from .slq import slq_log_quadratic
@@ -394,7 +394,7 @@ class CGGP(ClusterGP):
         fmu = anyd_matvec(self.fused_anyd, "knm", kernel.spec(Xnew.shape[1]), Xnew, iv.Z, a)  # Kmn^T a, :351 (row M1)
         return fmu + self._mean(Xnew), fvar
 
-    def predict_f_batched(self, X, batch_size, shared_inverse=False, inverse_threshold=None):
+    def predict_f_batched(self, X, batch_size, shared_inverse=False, inverse_threshold=None, fused_variance=False):
         """`batch_posterior_computation` (`cggp/cli_utils.py:426-436`); (Kmm+Lambda) and its solve
         against pseudo_u do not depend on the batch and are formed once.
 
@@ -404,10 +404,19 @@ class CGGP(ClusterGP):
         (M right-hand sides) and apply Y to every batch as one GEMM.  For N rows that is
         `iterations x 2 M^3 + 2 N M^2` flops instead of `iterations x 2 N M^2`.  The columns of I are
         solved to `inverse_threshold` (default: the model's threshold squared, so that the product
-        with a batch stays inside the per-batch solve's own tolerance)."""
+        with a batch stays inside the per-batch solve's own tolerance).
+
+        `fused_variance` (False, True or "auto"; with `shared_inverse=True` only): True forms the variance term
+        k(x, Z) Y k(Z, x) of each batch by one `ops.knm_quadform` (include/mgp_predict.h) -- no [B, M] kernel panel, half
+        the matrix-core work -- instead of `ops.k_dense`, `ops.symm_matmul` and a row sum; False is that composition,
+        bit for bit what this method computed before the option existed; "auto" follows
+        `conjugate_gradient.fused_variance_auto`."""
+        check_fused_variance(fused_variance)
         if shared_inverse and self.matrix_free:
             raise ValueError("shared_inverse=True forms the [M, M] inverse; matrix_free=True refuses it "
                              "(pass shared_inverse=False)")
+        if fused_variance is True and not shared_inverse:
+            raise ValueError("fused_variance=True applies the shared [M, M] inverse: pass shared_inverse=True")
         _, KmmLambda, _ = self._system()
         cg = self.conjugate_gradient
         a = cg(KmmLambda, self.pseudo_u)
@@ -428,6 +437,12 @@ class CGGP(ClusterGP):
         Y = (0.5 * (Y + Y.t())).contiguous()
         kernel, Z = self.kernel, self.inducing_variable.Z
         spec = kernel.spec(Z.shape[1])
+        if use_fused_variance(fused_variance, Y.dtype, Z.shape[1], M):
+            for s in range(0, X.shape[0], batch_size):
+                xb = X[s:s + batch_size]
+                variances.append((kernel.K_diag(xb) - ops.knm_quadform(spec, xb, Z, Y))[:, None])
+                means.append(anyd_matvec(self.fused_anyd, "knm", spec, xb, Z, a) + self._mean(xb))
+            return torch.cat(means, 0), torch.cat(variances, 0)
         for s in range(0, X.shape[0], batch_size):
             xb = X[s:s + batch_size]
             Knm = ops.k_dense(spec, xb, Z)  # [B, M] = Kmn^T
@@ -710,6 +725,7 @@ class SGPR:
         self._cg_S = None
         self._S = None
         self._KK = None
+        self._C = None
         self._key = self._fingerprint()
         # keep the fingerprinted tensors alive: id() of a freed tensor can be handed to the next one
         self._key_refs = (self.inducing_variable.Z, self.X, self.Y)
@@ -816,6 +832,70 @@ class SGPR:
             return mean, cov[None, ...]
         var = kernel.K_diag(Xnew) - ops.colwise_dot(Kms, W1) + self.likelihood.variance * ops.colwise_dot(Kms, W2)
         return mean, var[:, None]
+
+    def variance_matrix(self):
+        """C = (Kmm + jitter I)^-1 - s2 S^-1 [M, M], symmetric, so that var* = k_** - K_*m C K_m* (cached).
+
+        Formed without that subtraction, which cancels: with L = chol(Kmm + jitter I),
+        AAT = L^-1 (K_mn K_nm) L^-T / s2 and B = I + AAT (the matrices of `elbo`), S = s2 L B L^T and
+        C = L^-T (I - B^-1) L^-1 = L^-T (B^-1 AAT) L^-1.  K_mn K_nm is the all-reduced `kmn_knm()`, so the rows of X
+        may be this rank's shard."""
+        self._sync()
+        if self._C is None:
+            s2 = self.likelihood.variance
+            KK = self.kmn_knm()
+            L = torch.linalg.cholesky(self.operator().Kmm)  # Kmm + jitter I
+            T1 = torch.linalg.solve_triangular(L, KK, upper=False)
+            AAT = torch.linalg.solve_triangular(L, T1.t().contiguous(), upper=False) / s2
+            AAT = 0.5 * (AAT + AAT.t())
+            B = AAT + torch.eye(KK.shape[0], dtype=KK.dtype, device=KK.device)
+            G = torch.cholesky_solve(AAT, torch.linalg.cholesky(B))  # B^-1 AAT
+            G = 0.5 * (G + G.t())
+            # L^-T G L^-1: two triangular solves from the left, G symmetric
+            T2 = torch.linalg.solve_triangular(L.t(), G, upper=True)  # L^-T G
+            C = torch.linalg.solve_triangular(L.t(), T2.t().contiguous(), upper=True)  # L^-T (L^-T G)^T
+            self._C = (0.5 * (C + C.t())).contiguous()
+        return self._C
+
+    def predict_f_batched(self, X, batch_size=None, fused_variance="auto"):
+        """(mean [N, P], var [N, 1]) for all rows of X: what `predict_f` returns with `full_cov=False`, without its two
+        B-column solves per batch.  The mean is one K_*m alpha sweep over all rows; the variance is
+        k_** - K_*m C K_m* with the [M, M] matrix of `variance_matrix()`, in chunks of `batch_size` rows (None: one).
+
+        `fused_variance`: True forms K_*m C K_m* by `ops.knm_quadform` (include/mgp_predict.h: no [B, M] kernel panel,
+        the upper triangle of C on the matrix cores), False composes it from `ops.k_dense`, `ops.symm_matmul` and a row
+        sum, "auto" follows `conjugate_gradient.fused_variance_auto`."""
+        check_fused_variance(fused_variance)
+        self._sync()
+        kernel, Z = self.kernel, self.inducing_variable.Z
+        spec = kernel.spec(Z.shape[1])
+        mean = anyd_matvec(self.fused_anyd, "knm", spec, X, Z, self.alpha())
+        C = self.variance_matrix()
+        fused = use_fused_variance(fused_variance, C.dtype, Z.shape[1], Z.shape[0])
+        bs = batch_size or max(X.shape[0], 1)
+        variances = []
+        for s in range(0, X.shape[0], bs):
+            xb = X[s:s + bs]
+            if fused:
+                quad = ops.knm_quadform(spec, xb, Z, C)
+            else:
+                Knm = ops.k_dense(spec, xb, Z)  # [B, M]
+                quad = (Knm * ops.symm_matmul(C, Knm)).sum(dim=1)
+            variances.append((kernel.K_diag(xb) - quad)[:, None])
+        var = torch.cat(variances, 0) if variances else mean.new_empty((0, 1))
+        return mean, var
+
+    def predict_y(self, Xnew, full_cov=False, full_output_cov=False):
+        """`predict_f` plus the noise variance (GPflow `GPModel.predict_y` with a Gaussian likelihood).  It runs
+        `predict_f`'s two solves for all of Xnew at once: for many rows use `predict_y_batched`."""
+        assert not full_cov and not full_output_cov
+        mean, var = self.predict_f(Xnew)
+        return mean, var + self.likelihood.variance
+
+    def predict_y_batched(self, X, batch_size=None, fused_variance="auto"):
+        """`predict_f_batched` plus the noise variance: the whole-data-set form of `predict_y`."""
+        mean, var = self.predict_f_batched(X, batch_size, fused_variance)
+        return mean, var + self.likelihood.variance
 
     def elbo(self):
         """Titsias' collapsed bound, GPflow `SGPR.elbo` (const + logdet + quad + trace)."""
@@ -1219,10 +1299,16 @@ def sgpr_class(train_data, kernel, likelihood, iv, **kwargs):
     return SGPR(train_data, kernel, iv, noise_variance=likelihood.variance, **kwargs)
 
 
-def rmse_nlpd(model, test_data, batch_size=None):
-    """Test RMSE / NLPD as `make_metrics_callback` computes them (`cggp/optimize.py:302-309,344-350`)."""
+def rmse_nlpd(model, test_data, batch_size=None, batched=False):
+    """Test RMSE / NLPD as `make_metrics_callback` computes them (`cggp/optimize.py:302-309,344-350`).
+    `batched=True` predicts all rows by `model.predict_f_batched(x, batch_size)` where the model has one (the pieces
+    that do not depend on the rows are formed once); the default loops `predict_f`."""
     x, y = test_data
     bs = batch_size or x.shape[0]
+    if batched and hasattr(model, "predict_f_batched") and x.shape[0] > 0:
+        mu, var = model.predict_f_batched(x, bs)
+        lpd = model.likelihood.predict_log_density(x, mu, var, y).sum().item()
+        return math.sqrt(((y - mu) ** 2).sum().item() / x.shape[0]), -lpd / x.shape[0]
     sq, lpd, n = 0.0, 0.0, 0
     for s in range(0, x.shape[0], bs):
         xb, yb = x[s:s + bs], y[s:s + bs]

@@ -254,6 +254,32 @@ def knm_project(spec, Xs, X, R, want_proj=False, r_layout=COLS):
     return sqnorm, proj
 
 
+def knm_quadform(spec, Xs, Z, C):
+    """q [B] = k(xs_b, Z) C k(Z, xs_b) for a symmetric C [M, M] given by its upper triangle (`mgp_knm_quadform`,
+    include/mgp_predict.h): the entries below the diagonal are never read.  k(Xs, Z) is never formed on the fused route
+    (fp64, D <= 32).  C may be a row-major view with a row stride >= M (columns contiguous)."""
+    Xs = _points(Xs, "Xs", spec.D)
+    Z = _points(Z, "Z", spec.D, Xs.dtype)
+    B, M = Xs.shape[0], Z.shape[0]
+    if not torch.is_tensor(C) or C.dim() != 2 or tuple(C.shape) != (M, M):
+        raise ValueError(f"C must be [M={M}, M], got {tuple(C.shape) if torch.is_tensor(C) else type(C)}")
+    if C.dtype != Xs.dtype or C.device != Xs.device:
+        raise ValueError(f"C must be {Xs.dtype} on {Xs.device}, got {C.dtype} on {C.device}")
+    if M > 1 and C.stride(1) != 1:
+        raise ValueError("C must have contiguous columns")
+    ldc = C.stride(0) if M > 1 else max(M, 1)
+    if M > 1 and ldc < M:
+        raise ValueError(f"row stride {ldc} of C is less than M={M}")
+    q = torch.empty((B,), dtype=Xs.dtype, device=Xs.device)
+    if B > 0:
+        # M == 0 goes through the C-ABI too: libmgp writes the zeros
+        hd = _hip.get_handle(Xs.device)
+        k = spec.struct(_hip.dtype_code(Xs))
+        hd.check(hd.lib.mgp_knm_quadform(hd.h, ctypes.byref(k), _hip.ptr(Xs), B, _hip.ptr(Z), M, _hip.ptr(C), ldc,
+                                         _hip.ptr(q)))
+    return q
+
+
 def pcg_solve_record(op, rhs, error_threshold, max_iterations=None, min_float=1e-16, check_every=10,
                      preconditioner=None):
     """CG from zero on `op` (a `conjugate_gradient.LinearOperator`) for the rows of rhs [Bt, n], no residual refresh,
