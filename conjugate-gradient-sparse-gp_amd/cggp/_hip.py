@@ -185,6 +185,12 @@ PREDICT_SIGNATURES = {
     "mgp_knm_quadform": (_I, [_P, _KP, _P, _L, _P, _L, _P, _L, _P]),
 }
 
+# entry points declared in include/mgp_points.h (same library; tests/test_points_abi.py checks this table)
+POINTS_SIGNATURES = {
+    "mgp_k_dense_vjp_points": (_I, [_P, _KP, _P, _L, _P, _L, _P, _L, _L, ctypes.POINTER(_D), ctypes.POINTER(_D), _P,
+                                    _P]),
+}
+
 
 def lib_path():
     # MGP_LIBRARY lets A/B measurements load an experimental build; the default is the in-tree one
@@ -205,7 +211,7 @@ def load_library():
         lib = ctypes.CDLL(path)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items())
                                   + list(ANYD_SIGNATURES.items()) + list(SWEEP_ANYD_SIGNATURES.items())
-                                  + list(PREDICT_SIGNATURES.items())):
+                                  + list(PREDICT_SIGNATURES.items()) + list(POINTS_SIGNATURES.items())):
             fn = getattr(lib, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args

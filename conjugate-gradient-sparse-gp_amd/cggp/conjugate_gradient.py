@@ -151,6 +151,38 @@ def use_fused_anyd(fused_anyd, dtype, D, columns=1):
     return bool(fused_anyd)
 
 
+# `fused_point_grads="auto"` takes `ops.k_dense_vjp_points` (include/mgp_points.h) for the point gradients of a dense
+# kernel block [na, nb] where the fused call took at most 0.9 of the time of the torch route (`ops.k_dense_vjp` +
+# `training.k_grad_points`) at every measured point: fp64 device tensors, D <= FUSED_POINT_GRADS_AUTO_MAX_D (the
+# largest measured dimension) and na * nb >= FUSED_POINT_GRADS_AUTO_MIN_PAIRS (the smallest measured block, [4096, 256])
+# -- K_mm at M = 2048 .. 16384 and K_mn [4096, 256], [4096, 1000], SE at D = 8, Matern-3/2 at D = 32 and D = 77
+# (profiles/kvjp_points_times.json, "auto").  None for the pair count: no such region, "auto" means False.
+FUSED_POINT_GRADS_AUTO_MIN_PAIRS = 1 << 20
+FUSED_POINT_GRADS_AUTO_MAX_D = 77
+
+
+def check_fused_point_grads(fused_point_grads, name="fused_point_grads"):
+    """`fused_point_grads` as given, or `ValueError`: False, True or "auto"."""
+    return check_wide(fused_point_grads, name)
+
+
+def fused_point_grads_auto(dtype, D, na, nb):
+    """The rule behind `fused_point_grads="auto"`: fp64, D <= FUSED_POINT_GRADS_AUTO_MAX_D and a block of at least
+    FUSED_POINT_GRADS_AUTO_MIN_PAIRS pairs."""
+    return (FUSED_POINT_GRADS_AUTO_MIN_PAIRS is not None and dtype == torch.float64
+            and int(D) <= FUSED_POINT_GRADS_AUTO_MAX_D and int(na) * int(nb) >= FUSED_POINT_GRADS_AUTO_MIN_PAIRS)
+
+
+def use_fused_point_grads(fused_point_grads, A, B):
+    """Whether the point gradients of k(A, B) with this setting come from `ops.k_dense_vjp_points`.  fp32 tensors and
+    host tensors take the torch route whatever the setting: the entry point is fp64 device code only."""
+    if fused_point_grads is False or A.dtype != torch.float64 or B.dtype != torch.float64 or not (A.is_cuda and B.is_cuda):
+        return False
+    if fused_point_grads == "auto":
+        return fused_point_grads_auto(A.dtype, A.shape[1], A.shape[0], B.shape[0])
+    return True
+
+
 # `fused_variance="auto"` takes `ops.knm_quadform` (include/mgp_predict.h) for the whole-test-set variance k C k of
 # SGPR and CDGP where the fused kernel took at most 0.9 of the time of the composition (`ops.k_dense` + `ops.symm_matmul`
 # + row sum) at every measured point: fp64, D <= 32 and M >= FUSED_VARIANCE_AUTO_MIN_M, both measured kernels, B = 2^16

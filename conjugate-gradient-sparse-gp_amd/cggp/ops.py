@@ -384,6 +384,39 @@ def k_dense_vjp(spec, A, B, G):
     return dvar.value, [dls[d] for d in range(spec.D)]
 
 
+def k_dense_vjp_points(spec, A, B, G, need_dA=True, need_dB=True, panel_rows=0):
+    """(dL/dvariance: float, [dL/dl_d for d < D], dA [na, D] or None, dB [nb, D] or None) for K = k(A, B) given the dense
+    cotangent G = dL/dK [na, nb] (`mgp_k_dense_vjp_points`, include/mgp_points.h): the scalars of `k_dense_vjp` and the
+    point gradients of `training.k_grad_points` from fused pair kernels, no [., ., D] temporary.  fp64 and D <= 512;
+    G may be a row-major view with a row stride >= nb (anything else is copied); A and B may be the same tensor, and
+    dA + dB is then `training.kmm_grad_z(Z, G)`.  `panel_rows`: rows of A per panel, 0 = the library's rule."""
+    panel_rows = int(panel_rows)
+    if panel_rows < 0:
+        raise ValueError("panel_rows must be >= 0")
+    A = _points(A, "A", spec.D)
+    B = _points(B, "B", spec.D, A.dtype)
+    na, nb = A.shape[0], B.shape[0]
+    if not isinstance(G, torch.Tensor) or G.dim() != 2 or tuple(G.shape) != (na, nb):
+        raise ValueError(f"G must be [na={na}, nb={nb}], got {tuple(G.shape) if isinstance(G, torch.Tensor) else G}")
+    if G.dtype != A.dtype:
+        raise TypeError(f"G has dtype {G.dtype}, expected {A.dtype}")
+    if na and nb and not (G.stride(1) == 1 and G.stride(0) >= nb):
+        G = G.contiguous()
+    if not G.is_cuda:
+        raise RuntimeError(f"G must live on the GPU (got {G.device}); the hot path has no CPU fallback")
+    # one row: torch calls any row stride contiguous, and the library never steps by it
+    ldg = G.stride(0) if na > 1 and nb else nb
+    dA = torch.empty((na, spec.D), dtype=A.dtype, device=A.device) if need_dA else None
+    dB = torch.empty((nb, spec.D), dtype=A.dtype, device=A.device) if need_dB else None
+    dvar = ctypes.c_double(0.0)
+    dls = (ctypes.c_double * _hip.MGP_MAX_D)()
+    hd = _hip.get_handle(A.device)
+    k = spec.struct(_hip.dtype_code(A))
+    hd.check(hd.lib.mgp_k_dense_vjp_points(hd.h, ctypes.byref(k), _hip.ptr(A), na, _hip.ptr(B), nb, _hip.ptr(G), ldg,
+                                           panel_rows, ctypes.byref(dvar), dls, _hip.ptr(dA), _hip.ptr(dB)))
+    return dvar.value, [dls[d] for d in range(spec.D)], dA, dB
+
+
 def kmm_lambda_matvec(spec, Z, lam, V):
     """out [R,M] = V [R,M] @ (k(Z,Z) + diag(lam)), matrix-free (row M2)."""
     Z = _points(Z, "Z", spec.D)

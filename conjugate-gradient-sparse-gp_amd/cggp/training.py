@@ -21,7 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip, ops
-from .conjugate_gradient import ConjugateGradient, anyd_matvec, check_fused_anyd
+from .conjugate_gradient import (ConjugateGradient, anyd_matvec, check_fused_anyd, check_fused_point_grads,
+                                 use_fused_point_grads)
 from .kernels import Stationary
 from .models import check_data_term, check_pathwise, draw_pathwise, eval_logdet, rademacher
 
@@ -50,27 +51,36 @@ class Parameter:
 
 class _KBlock(torch.autograd.Function):
     """K = k(A, B) (+ jitter I): forward `mgp_k_dense`, backward `mgp_k_dense_vjp`; where A or B needs a gradient
-    (trainable inducing inputs) it comes from `k_grad_points`.  K(Z) passes Z twice and autograd adds the two."""
+    (trainable inducing inputs) it comes from `k_grad_points`.  K(Z) passes Z twice and autograd adds the two.
+    With `fused_point_grads` (the rule of `use_fused_point_grads`) a backward pass that needs a point gradient is ONE
+    `mgp_k_dense_vjp_points` call for the hyper-parameters and the sides that need one."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, A, B, kind, jitter):
+    def forward(ctx, variance, lengthscales, A, B, kind, jitter, fused_point_grads=False):
         D = A.shape[1]
         spec = ops.KernelSpec(kind, float(variance), [float(x) for x in lengthscales.reshape(-1)], D)
         ctx.spec, ctx.v_shape, ctx.l_shape = spec, variance.shape, lengthscales.shape
+        ctx.fused_point_grads = fused_point_grads
         ctx.save_for_backward(A, B)
         return ops.k_dense(spec, A, B, jitter=jitter)
 
     @staticmethod
     def backward(ctx, G):
         A, B = ctx.saved_tensors
-        dvar, dls = ops.k_dense_vjp(ctx.spec, A, B, G.contiguous())
+        need_a, need_b = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dA = dB = None
+        if (need_a or need_b) and use_fused_point_grads(ctx.fused_point_grads, A, B):
+            dvar, dls, dA, dB = ops.k_dense_vjp_points(ctx.spec, A.detach(), B.detach(), G, need_dA=need_a,
+                                                       need_dB=need_b)
+        else:
+            dvar, dls = ops.k_dense_vjp(ctx.spec, A, B, G.contiguous())
+            if need_a or need_b:
+                dA, dB = k_grad_points(ctx.spec.kind, ctx.spec.variance, ctx.spec.lengthscales, A, B, G)
         gv = torch.tensor(dvar, dtype=torch.float64).reshape(ctx.v_shape)
         n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
         gl = torch.tensor(dls if n_l > 1 else [sum(dls)], dtype=torch.float64).reshape(ctx.l_shape)
-        dA = dB = None
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            dA, dB = k_grad_points(ctx.spec.kind, ctx.spec.variance, ctx.spec.lengthscales, A, B, G)
-        return (gv, gl, dA if ctx.needs_input_grad[2] else None, dB if ctx.needs_input_grad[3] else None, None, None)
+        grads = (gv, gl, dA if need_a else None, dB if need_b else None, None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `fused_point_grads` is optional in apply()
 
 
 class TrainableKernel:
@@ -85,12 +95,18 @@ class TrainableKernel:
     def parameters(self):
         return [self.variance_p.raw, self.lengthscales_p.raw]
 
-    def K(self, X, X2=None, jitter=0.0):
+    def K(self, X, X2=None, jitter=0.0, fused_point_grads=False):
+        """k(X, X2) (+ jitter I) as an autograd node.  `fused_point_grads` (False, True or "auto"): where X or X2 needs a
+        gradient, the backward pass is one `ops.k_dense_vjp_points` call instead of `ops.k_dense_vjp` +
+        `k_grad_points` -- always (True) or by the measured rule (`conjugate_gradient.fused_point_grads_auto`).  fp32
+        tensors and host tensors take the torch route whatever the setting."""
         X2 = X if X2 is None else X2
         ls = self.lengthscales_p()
         if ls.dim() == 0:
             ls = ls.reshape(1)
-        return _KBlock.apply(self.variance_p(), ls, X, X2, self.name, float(jitter))
+        if check_fused_point_grads(fused_point_grads) is False:
+            return _KBlock.apply(self.variance_p(), ls, X, X2, self.name, float(jitter))
+        return _KBlock.apply(self.variance_p(), ls, X, X2, self.name, float(jitter), fused_point_grads)
 
     def frozen(self):
         """Plain kernel with the current values (non-differentiable fast paths: predict, metrics)."""
@@ -394,6 +410,12 @@ class TrainableCGGP:
     `wide_solves` (False, True or "auto"; with `matrix_free=True` only) is handed to every `KmmLambdaOperator`, as in
     `models.CGGP`.
 
+    `fused_point_grads` (False, True or "auto"; default False: the code above, bit for bit) is handed to every
+    `self.kernel.K(...)` block: with a trainable Z the backward pass of a block is then one `mgp_k_dense_vjp_points` call
+    (include/mgp_points.h) instead of `mgp_k_dense_vjp` + `k_grad_points` -- always (True) or where it was measured at
+    most 0.9 of the torch route (`conjugate_gradient.fused_point_grads_auto`).  The forward pass does not change; fp32
+    and host tensors take the torch route whatever the setting.
+
     `trainable_inducing=True` (the reference's `--tip`: `set_trainable(model.inducing_variable, tip)`,
     `paper_cli_geospatial.py:237`): the model keeps its own copy of Z as a leaf, `parameters()` ends with it and
     `frozen_model()` hands over a detached copy.  The dense model differentiates its kernel blocks in Z by
@@ -442,8 +464,9 @@ class TrainableCGGP:
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
                  num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
                  wide_solves=False, trainable_inducing=False, data_term="batch", num_bases=1024, num_samples=5,
-                 epsilon="matheron", fused_anyd=False):
+                 epsilon="matheron", fused_anyd=False, fused_point_grads=False):
         from .conjugate_gradient import check_wide
+        self.fused_point_grads = check_fused_point_grads(fused_point_grads)
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
@@ -493,7 +516,7 @@ class TrainableCGGP:
             ls = ls.reshape(1)
         var_f = var_p.to(device=dev, dtype=dt)
         lam = s2 / self.cluster_counts[:, 0]  # diag_variance, :226-228
-        Kmn = self.kernel.K(Z, x)  # :334
+        Kmn = self.kernel.K(Z, x, fused_point_grads=self.fused_point_grads)  # :334
         if probes is None:
             probes = rademacher((M, self.num_probes), dt, dev, self.probe_seed)
             self.probe_seed += 1
@@ -583,7 +606,7 @@ class TrainableCGGP:
             times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
             solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
         else:
-            Kmm = self.kernel.K(Z)  # :300 / :333
+            Kmm = self.kernel.K(Z, fused_point_grads=self.fused_point_grads)  # :300 / :333
             KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
             times_kzz = lambda V: Kmm @ V
             solve = lambda rhs: cg(KL, rhs)
@@ -643,7 +666,7 @@ class TrainableCGGP:
             times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
             solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
         else:
-            Kmm = self.kernel.K(Z)  # :300 / :333
+            Kmm = self.kernel.K(Z, fused_point_grads=self.fused_point_grads)  # :300 / :333
             KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
             times_kzz = lambda V: Kmm @ V
             solve = lambda rhs: cg(KL, rhs)
@@ -683,10 +706,10 @@ class TrainableCGGP:
         cg = self.conjugate_gradient
         s2 = self.noise_p().to(device=dev, dtype=dt)
         var_f = self.kernel.variance_p().to(device=dev, dtype=dt)
-        Kmm = self.kernel.K(self.Z)  # :300 / :333
+        Kmm = self.kernel.K(self.Z, fused_point_grads=self.fused_point_grads)  # :300 / :333
         lam = s2 / self.cluster_counts[:, 0]  # diag_variance, :226-228
         KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
-        Kmn = self.kernel.K(self.Z, x)  # :334
+        Kmn = self.kernel.K(self.Z, x, fused_point_grads=self.fused_point_grads)  # :334
         fused = self.fused_solves and not (self.num_probes is None and probes is None)
         reuse = fused
         if fused:
@@ -982,9 +1005,10 @@ class _SGPRElbo(torch.autograd.Function):
     """`models.SGPR.elbo` as an autograd node over (variance, lengthscales, s2, Kmm_j, Z).  Forward: Q by
     `mgp_kmn_knm`, b by `mgp_kmn_matvec`, y^T y, summed over ranks with `allreduce`, then `sgpr_bound`.  Backward:
     `sgpr_bound_adjoints`; the Kmm_j cotangent goes back to the caller (`TrainableKernel.K`, whose backward is
-    `mgp_k_dense_vjp`) and, for a trainable Z, through `kmm_grad_z`; the N-sized part is one `mgp_kmn_knm_vjp` call
-    (`mgp_kmn_knm_vjp_anyd` above D = 32), and its [dvariance, dl, dZ] partials are summed over ranks by ONE
-    all-reduce."""
+    `mgp_k_dense_vjp`) and, for a trainable Z, through `kmm_grad_z` -- or, when the model's `fused_point_grads` applies
+    and Kmm_j came without a graph, both through one `mgp_k_dense_vjp_points` call here; the N-sized part is one
+    `mgp_kmn_knm_vjp` call (`mgp_kmn_knm_vjp_anyd` above D = 32), and its [dvariance, dl, dZ] partials are summed over
+    ranks by ONE all-reduce."""
 
     @staticmethod
     def forward(ctx, variance, lengthscales, s2, Kmm_j, Z, model, X, Y):
@@ -1028,13 +1052,21 @@ class _SGPRElbo(torch.autograd.Function):
             nv, nl = float(buf[0]), buf[1:1 + D].tolist()
             if need_z:
                 nz = buf[1 + D:].reshape(M, D)
+        kz = None
+        if need_z and not ctx.needs_input_grad[3] and use_fused_point_grads(model.fused_point_grads, Zd, Zd):
+            # `TrainableSGPR.elbo` handed over a K_mm block without a graph: its whole VJP is this one call on (Z, Z),
+            # the hyper-parameter sums and both arguments of k(Z, Z) (the jitter is a constant)
+            kv, kl, dA, dB = ops.k_dense_vjp_points(spec, Zd, Zd, GK)
+            nv, nl, kz = nv + kv, [a + b for a, b in zip(nl, kl)], dA + dB
         gv = torch.tensor(g * (dvar + nv), dtype=torch.float64).reshape(ctx.v_shape)
         n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
         gl = torch.tensor([g * v for v in nl] if n_l > 1 else [g * sum(nl)], dtype=torch.float64).reshape(ctx.l_shape)
         gs = torch.tensor(g * ds2, dtype=torch.float64).reshape(ctx.s_shape)
         gZ = None
         if need_z:
-            gZ = g * (nz + kmm_grad_z(spec.kind, spec.variance, spec.lengthscales, Zd, GK))
+            if kz is None:
+                kz = kmm_grad_z(spec.kind, spec.variance, spec.lengthscales, Zd, GK)
+            gZ = g * (nz + kz)
         return gv, gl, gs, g * GK, gZ, None, None, None
 
 
@@ -1051,14 +1083,18 @@ class TrainableSGPR:
     D = 32 the N-sized part is `mgp_kmn_knm_vjp_anyd`, whose kernels stage the dimensions through LDS, and the
     constructor refuses X, Y, Z that are not on the GPU (ValueError).  `fused_anyd` (False, True or "auto"): the rule
     of the bound's `K_mn y` product and the setting of the frozen model, as on `models.SGPR`; `mgp_kmn_knm` and the VJP
-    are not affected."""
+    are not affected.  `fused_point_grads` (False, True or "auto"; default False): the K_mm block's setting -- with a
+    trainable Z its whole VJP, the hyper-parameter sums and the gradient in Z, is then ONE `mgp_k_dense_vjp_points` call
+    on (Z, Z) in place of `mgp_k_dense_vjp` + `kmm_grad_z` (always, or by the measured rule of
+    `conjugate_gradient.fused_point_grads_auto`); with a frozen Z, or with host tensors, nothing changes."""
 
     num_probes = None
     internal_data = True
 
     def __init__(self, kernel, noise_variance, X, Y, Z, *, jitter=1e-6, trainable_inducing=False, allreduce=None,
-                 num_data=None, conjugate_gradient=None, fused_anyd=False):
+                 num_data=None, conjugate_gradient=None, fused_anyd=False, fused_point_grads=False):
         self.fused_anyd = check_fused_anyd(fused_anyd)  # K_mn y of the bound, and the frozen model's sweeps
+        self.fused_point_grads = check_fused_point_grads(fused_point_grads)  # the K_mm block's gradient in Z
         for name, t in (("X", X), ("Y", Y), ("Z", Z)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
                 raise ValueError(f"TrainableSGPR needs fp64 tensors: {name} is "
@@ -1098,7 +1134,12 @@ class TrainableSGPR:
         ls = self.kernel.lengthscales_p()
         if ls.dim() == 0:
             ls = ls.reshape(1)
-        Kmm_j = self.kernel.K(self.Z.detach(), jitter=self.jitter)
+        Zd = self.Z.detach()
+        if self.trainable_inducing and use_fused_point_grads(self.fused_point_grads, Zd, Zd):
+            with torch.no_grad():  # the same forward call; `_SGPRElbo.backward` takes the block's whole VJP in one call
+                Kmm_j = self.kernel.K(Zd, jitter=self.jitter)
+        else:
+            Kmm_j = self.kernel.K(Zd, jitter=self.jitter)
         return _SGPRElbo.apply(self.kernel.variance_p(), ls, self.noise_p(), Kmm_j, self.Z, self, X, Y)
 
     def training_loss(self, data=None, probes=None):
