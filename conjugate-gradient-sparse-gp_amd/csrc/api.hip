@@ -116,6 +116,11 @@ extern "C" int mgp_create(mgp_handle** out, int device) {
     delete h;
     return MGP_E_NOMEM;
   }
+  if (hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming) != hipSuccess) {
+    h->order_ev = nullptr;
+    (void)mgp_destroy(h);
+    return MGP_E_HIP;
+  }
   *out = h;
   return MGP_OK;
 }
@@ -178,6 +183,7 @@ extern "C" int mgp_destroy(mgp_handle* h) {
   for (auto& e : h->aside_ev)
     if (e) (void)hipEventDestroy(e);
   if (h->aside_stream) (void)hipStreamDestroy(h->aside_stream);
+  if (h->order_ev) (void)hipEventDestroy(h->order_ev);
   if (h->ones) (void)hipFree(h->ones);
   if (h->dparams) (void)hipFree(h->dparams);
   if (h->anyd_sc) (void)hipFree(h->anyd_sc);
@@ -192,7 +198,15 @@ extern "C" int mgp_destroy(mgp_handle* h) {
 
 extern "C" int mgp_set_stream(mgp_handle* h, void* hip_stream) {
   if (!h) return MGP_E_BADARG;
-  h->stream = (hipStream_t)hip_stream;
+  hipStream_t next = (hipStream_t)hip_stream;
+  if (next == h->stream) return MGP_OK;  // every operation of the Python binding comes through here: no cost
+  // The arenas and the device copies of the kernel scales are shared by every call through this handle and the caller
+  // cannot see them, so it cannot order two streams' use of them itself: the incoming stream waits for what the
+  // outgoing one has been given so far.  (No caller switches streams inside a stream capture; the event is a plain
+  // record / wait pair and would be captured as a dependency if one did.)
+  MGP_HIP(h, hipEventRecord(h->order_ev, h->stream));
+  MGP_HIP(h, hipStreamWaitEvent(next, h->order_ev, 0));
+  h->stream = next;
   return MGP_OK;
 }
 

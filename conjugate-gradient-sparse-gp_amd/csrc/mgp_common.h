@@ -16,6 +16,10 @@
 struct mgp_handle {
   int device = 0;
   hipStream_t stream = nullptr;
+  // mgp_set_stream with another stream: recorded on the outgoing stream, waited for by the incoming one, so that the
+  // work enqueued through this handle runs in call order (the arenas below are shared by every call and invisible to
+  // the caller).  Created with the handle, destroyed with it; an unchanged stream never touches it.
+  hipEvent_t order_ev = nullptr;
   char err[512] = {0};
   // device workspace (partials of the two-stage reductions, CG state); grown on demand
   void* ws = nullptr;

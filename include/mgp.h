@@ -197,6 +197,11 @@ size_t mgp_workspace_bytes(const mgp_handle* h);
  * and fixed pool alike), which is how tests/test_gpu_buffer_contract.py knows which arenas an entry point reaches. */
 size_t mgp_arena_bytes(const mgp_handle* h, const char* name);
 int mgp_destroy(mgp_handle* h);
+/* The stream every later call enqueues on.  Work enqueued through one handle executes in call order, also when the
+ * stream changes in between: the handle's scratch is shared by all of its calls and invisible to the caller, who
+ * therefore cannot order two streams' use of it.  When hip_stream differs from the current stream, an event of the
+ * handle's own is recorded on the outgoing stream and the incoming stream waits for it (so the outgoing stream must
+ * still exist); the host does not wait.  Setting the stream that is already set costs nothing. */
 int mgp_set_stream(mgp_handle* h, void* hip_stream);
 const char* mgp_last_error(mgp_handle* h);
 /* name of the gfx arch the device code was built for, e.g. "gfx950" */

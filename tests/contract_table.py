@@ -1,4 +1,4 @@
-"""The buffer contract of every exported function of include/mgp.h that takes a device pointer, one row each.
+"""The buffer contract of every exported function of include/*.h that takes a device pointer, one row each.
 
 A row names the device inputs and outputs of its entry point, the regions of every output the header documents as
 written and as untouched, the reference and the bar of the test that already covers the arithmetic (quoted by test
@@ -1168,10 +1168,415 @@ class RffSample(Row):
         return "fused sweep" if (c["D"] <= 32 and c["S"] <= 8) else "feature panels + NT GEMM"
 
 
+# ------------------------------------------------------------------ the entry points of the five later headers
+def _num_cus():
+    """compute units of the device the call runs on (the chunk rule of a bound depends on it); the nominal 256 of an
+    MI355X where there is no GPU (the host tests evaluate references only)"""
+    return torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+
+
+class _SweepAnyd(Row):
+    """mgp_knm_matvec_anyd / mgp_kmn_matvec_anyd / mgp_kxx_matvec_anyd (include/mgp_sweep_anyd.h): `na` owned points
+    (the rows of the result), `nb` streamed ones, R columns.  fp64 above 32 dimensions is the fused route, held to
+    `dense_reference` of tests/test_gpu_sweep_anyd.py (the long-double product and the bound built on
+    `pair_reference.pair_bound`) on that test's own inputs; fp32 and D <= 32 are, by the header, exactly the code of
+    the plain name, and are held to the plain rows' bar (`kbar`) against the float64 oracle."""
+    entry = None
+    # fused route: `ws` alone (both squared-norm vectors and the chunk partials).  The fallbacks are the plain names':
+    # fp64 D = 17 the packed streamed set (and, R > 1, the transposed weights in `gen`), fp32 above D = 32 the panels
+    arenas = ("ws", "gen", "pack")
+
+    def _case(self, c):
+        from sweep_anyd_plan import Case
+        return Case(self.entry, c["kind"], c["D"], c["na"], c["nb"], c["R"], c["wl"], c["ol"], c.get("s2", 0.0))
+
+    def _fused(self, c, dt):
+        return dt == "f64" and c["D"] > 32
+
+    @staticmethod
+    def dense_bound(case, A, B, ls, W):
+        """(want, tol) of `dense_reference` (tests/test_gpu_sweep_anyd.py) for given points, lengthscales and
+        multipliers; `reference` below holds the two to each other bit for bit on every case of the table"""
+        import pair_reference as pr
+        u = 2.0 ** -53
+        pv = pr.pair_values(case.kind, VAR, ls, A, B)
+        rel = pr.pair_bound(case.kind, VAR, pv.s, pv.q, pr.scaled(case.kind, ls, A), pr.scaled(case.kind, ls, B),
+                            case.D, np.float64)
+        Wl = W.astype(LD)
+        want = pv.k @ Wl
+        tol = (rel.astype(LD) * pv.k) @ np.abs(Wl) + (case.nb + 2) * u * (pv.k @ np.abs(Wl))
+        if case.entry == "kxx":
+            want = want + LD(case.s2) * Wl
+            tol = tol + u * (np.abs(want) + LD(case.s2) * np.abs(Wl))
+        return want, tol
+
+    def ins(self, c, dt, rng):
+        from sweep_anyd_plan import points as anyd_points
+        case = self._case(c)
+        A, B, ls = anyd_points(case)
+        # the multipliers of `dense_reference`, restated: its rng, its shape
+        W = np.random.default_rng([7, case.na, case.nb, case.R]).standard_normal((case.nb, case.R))
+        d = dict(A=A, V=W if c["wl"] == COLS else np.ascontiguousarray(W.T), _ls=ls)
+        if self.entry != "kxx":
+            d["B"] = B
+        return d
+
+    def outs(self, c, dt):
+        return dict(out=(_vec(c["ol"], c["na"] or 2, c["R"]), "T"))
+
+    def call(self, lib, h, c, dt, p):
+        k = kstruct(c["kind"], dt, c["D"], p["_ls"])
+        if self.entry == "kxx":
+            return lib.mgp_kxx_matvec_anyd(h, ctypes.byref(k), p["A"], c["na"], c["s2"], p["V"], c["R"], c["wl"],
+                                           p["out"], c["ol"]), {}
+        if self.entry == "knm":  # X owned, Z streamed
+            return lib.mgp_knm_matvec_anyd(h, ctypes.byref(k), p["A"], c["na"], p["B"], c["nb"], p["V"], c["R"],
+                                           c["wl"], p["out"], c["ol"]), {}
+        return lib.mgp_kmn_matvec_anyd(h, ctypes.byref(k), p["B"], c["nb"], p["A"], c["na"], p["V"], c["R"], c["wl"],
+                                       p["out"], c["ol"]), {}
+
+    def reference(self, c, dt, ins):
+        if c["na"] == 0 or c["nb"] == 0:
+            return None
+        if self._fused(c, dt):
+            from test_gpu_sweep_anyd import dense_reference
+            case = self._case(c)
+            W = _as_cols(ins["V"], c["wl"])
+            B = ins["B"] if "B" in ins else ins["A"]
+            # `dense_reference` draws its own lengthscales: a call sequence that changes them
+            # (tests/test_gpu_call_sequences.py) gets the same bound from the same functions on the values it used
+            want, tol = self.dense_bound(case, ins["A"], B, ins["_ls"], W)
+            A0, B0, ls0, W0, want0, tol0 = dense_reference(case)
+            if np.array_equal(ls0, ins["_ls"]):  # the table's own inputs: the existing test's reference, to the bit
+                assert np.array_equal(A0, ins["A"]) and np.array_equal(B0, B) and np.array_equal(W0, W)
+                assert np.array_equal(want0, want) and np.array_equal(tol0, tol)
+            return want.astype(np.float64), tol.astype(np.float64)
+        A = rnd(ins["A"], dt)
+        V = _as_cols(rnd(ins["V"], dt), c["wl"])
+        K = ok.Kernel(c["kind"], VAR, ins["_ls"]).K(A, rnd(ins["B"], dt) if "B" in ins else A)
+        return K @ V + c.get("s2", 0.0) * V if self.entry == "kxx" else K @ V
+
+    def check(self, c, dt, ins, got, ref):
+        if c["na"] == 0:  # no owned point: nothing is written
+            return dict(out=none(got["out"].shape))
+        g = _as_cols(got["out"], c["ol"])
+        if c["nb"] == 0:  # no streamed point: zeros
+            assert not g.any(), (self.name, c, dt)
+            return dict(out=None)
+        if self._fused(c, dt):
+            want, tol = ref
+            ratio = float(np.max(np.abs(g.astype(LD) - want) / tol))
+            assert np.all(np.isfinite(g)) and ratio <= 1.0, (self.name, c, dt, ratio)
+        else:
+            e = relerr(g, ref)
+            assert e < kbar(c["kind"], dt), (self.name, c, dt, e)
+        return dict(out=None)
+
+
+def _anyd_cases(extra):
+    # owned block 128, streamed tile 64, K slices of 32 columns: (129, 65) two owned blocks and two chunks, (129, 150)
+    # three chunks (the partials of `ws`); D = 33 a slice and one k-step, 63 two whole slices and one k-step, 77 two
+    # and a half; R = 9 a pass of 8 and one of 1
+    return [dict(na=1, nb=1, D=33, R=1, kind="se", wl=COLS, ol=COLS),
+            dict(na=129, nb=65, D=63, R=3, kind="matern32", wl=ROWS, ol=ROWS),
+            dict(na=129, nb=150, D=77, R=9, kind="matern52", wl=COLS, ol=ROWS),
+            dict(na=129, nb=65, D=17, R=3, kind="se", wl=ROWS, ol=COLS)] + extra  # D = 17: the plain route
+
+
+class KnmMatvecAnyd(_SweepAnyd):
+    name = "mgp_knm_matvec_anyd"
+    entry = "knm"
+    cases = _anyd_cases([dict(na=65, nb=0, D=33, R=3, kind="se", wl=COLS, ol=COLS),    # M = 0: zeros
+                         dict(na=0, nb=65, D=33, R=3, kind="se", wl=COLS, ol=COLS)])   # N = 0: nothing written
+
+
+class KmnMatvecAnyd(_SweepAnyd):
+    name = "mgp_kmn_matvec_anyd"
+    entry = "kmn"
+    cases = _anyd_cases([dict(na=65, nb=0, D=33, R=3, kind="se", wl=COLS, ol=COLS),    # N = 0: zeros
+                         dict(na=0, nb=65, D=33, R=3, kind="se", wl=COLS, ol=COLS)])   # M = 0: nothing written
+
+
+class KxxMatvecAnyd(_SweepAnyd):
+    name = "mgp_kxx_matvec_anyd"
+    entry = "kxx"
+    # the D = 17 fallback on a MGP_KXX=sym handle is csrc/kxx.hip for fp64
+    arenas = ("ws", "gen", "kxx")
+    cases = [dict(na=1, nb=1, D=33, R=1, kind="se", wl=COLS, ol=COLS, s2=0.37),
+             dict(na=129, nb=129, D=63, R=3, kind="matern32", wl=ROWS, ol=ROWS, s2=0.37),
+             dict(na=150, nb=150, D=77, R=9, kind="matern52", wl=COLS, ol=ROWS, s2=0.37),
+             dict(na=129, nb=129, D=17, R=3, kind="se", wl=ROWS, ol=COLS, s2=0.37),
+             dict(na=0, nb=0, D=33, R=3, kind="se", wl=COLS, ol=COLS, s2=0.37)]  # N = 0: nothing written
+
+
+class KmnKnmVjpAnyd(Row):
+    """mgp_kmn_knm_vjp_anyd (include/mgp_anyd.h): host dvariance, dlengthscales; dZ[M, D] (may be NULL); Gq may be NULL
+    with P >= 1.  Above 32 dimensions: `kvjp_reference` and the derived bound of tests/test_gpu_sgpr_train_anyd.py
+    (`_check`, called as it stands).  At D <= 32 the header promises the implementation and the bits of
+    mgp_kmn_knm_vjp: the 1e-10 of the sum of |terms| of that row (test_kmn_knm_vjp_against_long_double), the companions
+    being those of `kvjp_reference`."""
+    name = "mgp_kmn_knm_vjp_anyd"
+    dtypes = ("f64",)
+    arenas = ("kgrad",)
+    poison = "finite"  # fp64 only: a larger finite problem
+    poison_case = dict(N=300, M=140, D=65, P=2, panel_rows=0, gq=True, dZ=True, kind="matern52")
+    host_scalars = True
+    VARIANCE = 1.4
+    # N = 130, M = 70: two 64-row tiles and two rows, 64 + 6 columns; panel_rows = 33: four panels, the last of 31 rows
+    cases = [dict(N=130, M=70, D=33, P=1, panel_rows=0, gq=True, dZ=True, kind="se"),
+             dict(N=130, M=70, D=65, P=2, panel_rows=33, gq=True, dZ=True, kind="matern32"),
+             dict(N=130, M=70, D=33, P=1, panel_rows=33, gq=False, dZ=True, kind="matern52"),  # Gq = NULL
+             dict(N=65, M=37, D=5, P=0, panel_rows=33, gq=True, dZ=True, kind="matern32"),
+             dict(N=130, M=70, D=65, P=0, panel_rows=0, gq=True, dZ=False, kind="matern12"),   # dZ = NULL
+             dict(N=0, M=37, D=33, P=1, panel_rows=0, gq=True, dZ=True, kind="se")]            # N = 0: zeros
+
+    def reads_pointer(self, c, dt):
+        return c["P"] > 0  # Y and Gb enter the NT GEMM, whose vector form reads their alignment (as mgp_kmn_knm_vjp)
+
+    def ins(self, c, dt, rng):
+        n = max(c["N"], 1)  # N = 0: one row allocated, none read
+        d = dict(X=rng.uniform(-1.5, 1.5, (n, c["D"])), Z=rng.uniform(-1.5, 1.5, (c["M"], c["D"])),
+                 _ls=math.sqrt(c["D"]) * np.linspace(0.7, 1.3, c["D"]))
+        if c["gq"]:
+            d["Gq"] = rng.standard_normal((c["M"], c["M"]))
+        if c["P"]:
+            d["Y"], d["Gb"] = rng.standard_normal((n, c["P"])), rng.standard_normal((c["M"], c["P"]))
+        return d
+
+    def outs(self, c, dt):
+        return dict(dZ=((c["M"], c["D"]), "T")) if c["dZ"] else {}
+
+    def call(self, lib, h, c, dt, p):
+        k = kstruct(c["kind"], dt, c["D"], p["_ls"], var=self.VARIANCE)
+        dv, dl = ctypes.c_double(float("nan")), (ctypes.c_double * _hip.MGP_MAX_D)()
+        rc = lib.mgp_kmn_knm_vjp_anyd(h, ctypes.byref(k), p["X"], c["N"], p["Z"], c["M"], p.get("Gq"), p.get("Y"),
+                                      p.get("Gb"), c["P"], c["panel_rows"], ctypes.byref(dv), dl, p.get("dZ"))
+        return rc, dict(dv=dv.value, dl=np.array([dl[d] for d in range(c["D"])]))
+
+    def reference(self, c, dt, ins):
+        from kvjp_reference import kvjp_reference
+        N = c["N"]
+        return kvjp_reference(c["kind"], self.VARIANCE, ins["_ls"], ins["X"][:N], ins["Z"], ins.get("Gq"),
+                              ins["Y"][:N] if c["P"] else None, ins.get("Gb"))
+
+    def check(self, c, dt, ins, got, ref):
+        f = lambda a: np.asarray(a, dtype=np.float64)
+        if c["N"] == 0:  # every companion sum is 0: the bound demands exact zeros (`_check` prints err / bound)
+            assert got["dv"] == 0.0 and not got["dl"].any() and not got["dZ"].any(), (self.name, c)
+            assert float(ref.sv) == 0.0 and not f(ref.dv).any() and not f(ref.dZ).any()
+        elif c["D"] > 32:
+            from test_gpu_sgpr_train_anyd import _check
+            dZ = torch.from_numpy(np.ascontiguousarray(got["dZ"])) if c["dZ"] else None
+            _check((got["dv"], list(got["dl"]), dZ), ref, c["N"], c["M"], c["D"], c["P"], c["dZ"])
+        else:
+            assert abs(got["dv"] - float(ref.dv)) <= 1e-10 * float(ref.sv), (self.name, c, got["dv"], float(ref.dv))
+            assert np.all(np.abs(got["dl"] - f(ref.dl)) <= 1e-10 * f(ref.sl)), (self.name, c)
+            if c["dZ"]:
+                assert np.all(np.abs(got["dZ"] - f(ref.dZ)) <= 1e-10 * f(ref.sz) + 1e-300), (self.name, c)
+        return dict(dZ=None) if c["dZ"] else {}
+
+    def route(self, c, dt, ptrs, num_cus=256):
+        return "panel GEMMs (vector form by alignment of Y, Gb)"
+
+
+class KDenseVjpPoints(Row):
+    """mgp_k_dense_vjp_points (include/mgp_points.h): host dvariance, dlengthscales; dA[na, D], dB[nb, D] (either may
+    be NULL); G[na, ldg] with NaN in the columns nb..ldg-1, which are never read; A and B may be one pointer.
+    `k_dense_vjp_points_reference` at `VJP_BAR` of each output's sum of |terms| (tests/test_gpu_kvjp_points.py)."""
+    name = "mgp_k_dense_vjp_points"
+    dtypes = ("f64",)
+    arenas = ("kgrad",)
+    poison = "finite"  # fp64 only: a larger finite problem
+    poison_case = dict(na=300, nb=300, D=65, pad=3, panel_rows=0, null=(), same=False, kind="matern52")
+    host_scalars = True
+    # DP = 4, 32 and the two staged routes (two and three slices of 32 dimensions); 257 = a block of 256 lanes and one;
+    # panel_rows = 33: panels of 33 rows, the last shorter
+    cases = [dict(na=1, nb=37, D=3, pad=3, panel_rows=0, null=(), same=False, kind="se"),
+             dict(na=257, nb=130, D=32, pad=3, panel_rows=33, null=(), same=False, kind="matern12"),
+             dict(na=130, nb=257, D=33, pad=3, panel_rows=0, null=("dA",), same=False, kind="matern32"),
+             dict(na=257, nb=130, D=65, pad=3, panel_rows=33, null=("dB",), same=False, kind="matern52"),
+             dict(na=130, nb=130, D=33, pad=3, panel_rows=0, null=(), same=True, kind="se"),   # A is B
+             dict(na=0, nb=37, D=3, pad=3, panel_rows=0, null=(), same=False, kind="se")]      # na = 0: zeros
+
+    def ins(self, c, dt, rng):
+        na = max(c["na"], 1)  # na = 0: one row allocated, none read
+        G = np.full((na, c["nb"] + c["pad"]), np.nan)  # NaN in the pad columns: it must not reach a result
+        G[:, :c["nb"]] = rng.standard_normal((na, c["nb"]))
+        d = dict(A=rng.uniform(-2.0, 2.0, (na, c["D"])), G=G, _ls=np.linspace(0.7, 1.4, c["D"]) * math.sqrt(c["D"]))
+        if not c["same"]:
+            d["B"] = rng.uniform(-2.0, 2.0, (c["nb"], c["D"]))
+        return d
+
+    def outs(self, c, dt):
+        d = dict(dA=((max(c["na"], 1), c["D"]), "T"), dB=((c["nb"], c["D"]), "T"))
+        return {k: v for k, v in d.items() if k not in c["null"]}
+
+    def call(self, lib, h, c, dt, p):
+        k = kstruct(c["kind"], dt, c["D"], p["_ls"])
+        dv, dl = ctypes.c_double(float("nan")), (ctypes.c_double * _hip.MGP_MAX_D)()
+        rc = lib.mgp_k_dense_vjp_points(h, ctypes.byref(k), p["A"], c["na"], p["A"] if c["same"] else p["B"], c["nb"],
+                                        p["G"], c["nb"] + c["pad"], c["panel_rows"], ctypes.byref(dv), dl, p.get("dA"),
+                                        p.get("dB"))
+        return rc, dict(dv=dv.value, dl=np.array([dl[d] for d in range(c["D"])]))
+
+    KEYS = ("dv", "dl", "dA", "dB", "sv", "sl", "sA", "sB")
+
+    def reference(self, c, dt, ins):
+        from kvjp_points_reference import k_dense_vjp_points_reference
+        na = c["na"]
+        A = ins["A"][:na]
+        ref = k_dense_vjp_points_reference(c["kind"], VAR, ins["_ls"], A, A if c["same"] else ins["B"],
+                                           ins["G"][:na, :c["nb"]])
+        return tuple(np.asarray(ref[k]) for k in self.KEYS)
+
+    def check(self, c, dt, ins, got, ref):
+        from kvjp_points_reference import VJP_BAR, excess
+        ref = dict(zip(self.KEYS, ref))
+        names = [n for n in ("dA", "dB") if n not in c["null"]]
+        for n in ["dv", "dl"] + names:
+            g = got[n][:c["na"]] if n == "dA" else got[n]
+            assert np.all(np.isfinite(g)), (self.name, c, n)
+            e = excess(g, ref[n], ref["s" + n[1:]], VJP_BAR)
+            assert e <= 1.0, (self.name, c, n, e)
+        written = {n: None for n in names}
+        if c["na"] == 0:
+            assert got["dv"] == 0.0 and not got["dl"].any() and not got["dB"].any(), (self.name, c)
+            written["dA"] = none(got["dA"].shape)  # no row of A: nothing to write
+        return written
+
+
+class RffSampleVjp(Row):
+    """mgp_rff_sample_vjp (include/mgp_pathwise.h): dtheta[L, D], dX[N, D], either may be NULL; G [S, N] or [N, S].
+    `rff_vjp_reference.vjp` and `rff_vjp_reference.bounds`, the bound the header states (tests/test_gpu_rff_vjp.py)."""
+    name = "mgp_rff_sample_vjp"
+    dtypes = ("f64",)
+    arenas = ("gen", "ws")  # the streamed records; the chunk partials
+    poison = "finite"  # fp64 only: a larger finite problem
+    poison_case = dict(N=300, L=300, D=32, S=8, layout=ROWS, null=())
+    # DP = 4, 8, 16, 32; (33, 257): two streamed chunks for dtheta and a second owner block of one basis; (257, 1) the
+    # reverse; (70, 255): three chunks of rows, eight of bases
+    cases = [dict(N=33, L=257, D=1, S=1, layout=ROWS, null=()),
+             dict(N=257, L=1, D=8, S=8, layout=COLS, null=()),
+             dict(N=70, L=255, D=9, S=8, layout=ROWS, null=("dX",)),
+             dict(N=70, L=255, D=32, S=1, layout=COLS, null=("dtheta",)),
+             dict(N=0, L=37, D=8, S=1, layout=ROWS, null=()),   # N = 0: zeros to dtheta, nothing to dX
+             dict(N=33, L=0, D=9, S=8, layout=COLS, null=())]   # L = 0: zeros to dX, nothing to dtheta
+
+    def _scale(self, c):
+        return math.sqrt(1.7 / max(c["L"], 1))
+
+    def ins(self, c, dt, rng):
+        n, l = max(c["N"], 1), max(c["L"], 1)  # an empty side: one row allocated, none read
+        return dict(X=rng.standard_normal((n, c["D"])), theta=rng.standard_normal((l, c["D"])),
+                    W=rng.standard_normal((c["S"], 2 * l)),
+                    G=rng.standard_normal((c["S"], n) if c["layout"] == ROWS else (n, c["S"])))
+
+    def outs(self, c, dt):
+        d = dict(dtheta=((max(c["L"], 1), c["D"]), "T"), dX=((max(c["N"], 1), c["D"]), "T"))
+        return {k: v for k, v in d.items() if k not in c["null"]}
+
+    def call(self, lib, h, c, dt, p):
+        return lib.mgp_rff_sample_vjp(h, CODE[dt], p["X"], c["N"], c["D"], p["theta"], c["L"], p["W"], c["S"],
+                                      self._scale(c), p["G"], c["layout"], p.get("dtheta"), p.get("dX")), {}
+
+    def _args(self, c, ins):
+        N, L = c["N"], c["L"]
+        G = ins["G"] if c["layout"] == ROWS else ins["G"].T
+        W = ins["W"] if L else ins["W"][:, :0]
+        return ins["X"][:N], ins["theta"][:L], W, self._scale(c), G[:, :N]
+
+    def reference(self, c, dt, ins):
+        from rff_vjp_reference import vjp
+        return vjp(*self._args(c, ins))
+
+    def check(self, c, dt, ins, got, ref):
+        from rff_vjp_reference import bounds
+        N, L = c["N"], c["L"]
+        if N == 0 or L == 0:  # no streamed term: zeros for every owner; no owner: nothing written
+            assert not got["dtheta"][:L].any() and not got["dX"][:N].any(), (self.name, c)
+            return dict(dtheta=None if L else none(got["dtheta"].shape), dX=None if N else none(got["dX"].shape))
+        written = {}
+        for n, r, b in zip(("dtheta", "dX"), ref, bounds(*self._args(c, ins), _num_cus())):
+            if n in c["null"]:
+                continue
+            err = np.abs(got[n] - r.astype(np.float64))
+            assert np.all(np.isfinite(got[n])) and np.all(err <= b), (self.name, c, n,
+                                                                     float(np.max(err / np.where(b > 0, b, 1.0))))
+            written[n] = None
+        return written
+
+
+class KnmQuadform(Row):
+    """mgp_knm_quadform (include/mgp_predict.h): q[B] = k(xs_b, Z) C k(Z, xs_b) for the upper triangle of C[M, ldc]; the
+    lower triangle and the columns M..ldc-1 hold NaN and are never read.  `quadform_reference.form` and `.bound` on
+    `pair_reference.pair_bound`, as tests/test_gpu_quadform.py holds both routes to them."""
+    name = "mgp_knm_quadform"
+    arenas = ("prj",)  # fused: block partials and the packed Z; generic (fp32, D = 33): sym(C) and two panels (no NT
+                       # GEMM slices in `ws` below M = 512)
+    PAD = 3
+    # tile 128 x 128, inner step 16: M = 127 / 129 / 257 one block short, two, three (the middle one paired with itself)
+    cases = [dict(B=1, M=1, D=5, kind="se"), dict(B=129, M=127, D=32, kind="matern32"),
+             dict(B=129, M=257, D=5, kind="matern52"), dict(B=1, M=129, D=33, kind="se"),
+             dict(B=0, M=37, D=5, kind="se"),    # B = 0: nothing written
+             dict(B=129, M=0, D=5, kind="se")]   # M = 0: zeros
+
+    def reads_pointer(self, c, dt):
+        return dt == "f32" or c["D"] > 32  # the generic route's NT GEMM picks its loads by alignment
+
+    def ins(self, c, dt, rng):
+        import pair_reference as pr
+        B, M, D = max(c["B"], 1), max(c["M"], 1), c["D"]  # an empty side: one row allocated, none read
+        Xs, Z = 1.2 * rng.standard_normal((B, D)) / math.sqrt(D), 1.2 * rng.standard_normal((M, D)) / math.sqrt(D)
+        if M > 5:
+            Z[5] = Xs[0]  # a coincident pair: k = variance, the Matern cusp
+        Gm = rng.standard_normal((M, M))
+        C = np.full((M, M + self.PAD), np.nan)  # NaN below the diagonal and in the pad columns
+        C[:, :M] = Gm @ Gm.T / M + np.diag(0.5 + rng.random(M))
+        C[np.tril_indices(M, -1)] = np.nan
+        return dict(Xs=Xs, Z=Z, C=C, _ls=pr.lengthscales(D))
+
+    def outs(self, c, dt):
+        return dict(q=((max(c["B"], 1),), "T"))
+
+    def call(self, lib, h, c, dt, p):
+        import pair_reference as pr
+        k = kstruct(c["kind"], dt, c["D"], p["_ls"], var=pr.VARIANCE)
+        return lib.mgp_knm_quadform(h, ctypes.byref(k), p["Xs"], c["B"], p["Z"], c["M"], p["C"],
+                                    max(c["M"], 1) + self.PAD, p["q"]), {}
+
+    def reference(self, c, dt, ins):
+        import pair_reference as pr
+        import quadform_reference as qr
+        B, M = c["B"], c["M"]
+        if B == 0 or M == 0:
+            return None
+        Xs, Z, C = rnd(ins["Xs"], dt), rnd(ins["Z"], dt), rnd(ins["C"][:, :M], dt)
+        pv = pr.pair_values(c["kind"], pr.VARIANCE, ins["_ls"], Xs, Z)
+        q, mag = qr.form(pv.k, C)
+        eps = qr.row_eps(c["kind"], pr.VARIANCE, ins["_ls"], Xs, Z, pv, NP[dt])[:, -1]
+        return np.asarray(q, dtype=np.float64), qr.bound(eps, M, mag, NP[dt])
+
+    def check(self, c, dt, ins, got, ref):
+        if c["B"] == 0:
+            return dict(q=none(got["q"].shape))
+        if c["M"] == 0:
+            assert not got["q"].any(), (self.name, c, dt)
+            return dict(q=None)
+        q, bound = ref
+        g = got["q"].astype(np.float64)
+        assert np.all(np.isfinite(g)) and np.all(np.abs(g - q) <= bound), (self.name, c, dt,
+                                                                           float(np.max(np.abs(g - q) / bound)))
+        return dict(q=None)
+
+    def route(self, c, dt, ptrs, num_cus=256):
+        return "fused" if (dt == "f64" and c["D"] <= 32) else "generic (sym(C), panels through mgp_k_dense, NT GEMM)"
+
+
 TABLE = [KnmMatvec(), KmnMatvec(), KDense(), KmnKnm(), KmnSqColsum(), KxxMatvec(), KxxPivchol(), LowrankApply(),
          KnmProject(), KxxGrad(), KmnKnmVjp(), SymmMatmul(), PcgSolve(), PcgSolveRecord(), OperatorApply(),
          KmmLambdaMatvec(), ColwiseDot(), DotAll(), NearestCenter(), ClusterStats(), SegmentSums(), KDenseVjp(),
-         RffFeatures(), RffSample()]
+         RffFeatures(), RffSample(), KnmMatvecAnyd(), KmnMatvecAnyd(), KxxMatvecAnyd(), KmnKnmVjpAnyd(),
+         KDenseVjpPoints(), RffSampleVjp(), KnmQuadform()]
 BY_NAME = {r.name: r for r in TABLE}
 
 

@@ -1,24 +1,32 @@
-"""tests/contract_table.py against include/mgp.h: every exported function is either a row of the table or excluded with
-a reason, and the table is well formed (no GPU needed)."""
+"""tests/contract_table.py against every header of include/: every exported function is either a row of the table or
+excluded with a reason, and the table is well formed (no GPU needed)."""
 
 import numpy as np
 
 import contract_table as ct
-from test_abi import declared_symbols
+from test_abi import declared_symbols, declared_symbols_by_header
 
 EXPECTED_ROWS = """mgp_knm_matvec mgp_kmn_matvec mgp_k_dense mgp_kmn_knm mgp_kmn_sq_colsum mgp_kxx_matvec mgp_kxx_pivchol
 mgp_lowrank_apply mgp_knm_project mgp_kxx_grad mgp_kmn_knm_vjp mgp_symm_matmul mgp_pcg_solve mgp_pcg_solve_record
 mgp_operator_apply mgp_kmm_lambda_matvec mgp_colwise_dot mgp_dot_all mgp_nearest_center mgp_cluster_stats
-mgp_segment_sums mgp_k_dense_vjp mgp_rff_features mgp_rff_sample""".split()
+mgp_segment_sums mgp_k_dense_vjp mgp_rff_features mgp_rff_sample mgp_knm_matvec_anyd mgp_kmn_matvec_anyd
+mgp_kxx_matvec_anyd mgp_kmn_knm_vjp_anyd mgp_k_dense_vjp_points mgp_rff_sample_vjp mgp_knm_quadform""".split()
+
+HEADERS = ["mgp.h", "mgp_anyd.h", "mgp_pathwise.h", "mgp_points.h", "mgp_predict.h", "mgp_sweep_anyd.h"]
 
 
 def test_every_exported_function_is_a_row_or_excluded_with_a_reason():
-    names = declared_symbols()
+    by_header = declared_symbols_by_header()
+    assert sorted(by_header) == HEADERS and by_header["mgp.h"] == declared_symbols()
+    assert all(by_header[hd] for hd in HEADERS), "a header that declares nothing: the expression no longer matches it"
+    names = sorted(set(n for v in by_header.values() for n in v))
+    assert sum(len(v) for v in by_header.values()) == len(names)  # no function is declared twice
     rows = [r.name for r in ct.TABLE]
-    assert len(rows) == len(set(rows)) == 24 and sorted(rows) == sorted(EXPECTED_ROWS)
-    for n in names:
-        assert (n in ct.BY_NAME) != (n in ct.EXCLUDED), f"{n}: exported by include/mgp.h, " \
-            "needs exactly one of a row in tests/contract_table.py or an entry of EXCLUDED"
+    assert len(rows) == len(set(rows)) == 31 and sorted(rows) == sorted(EXPECTED_ROWS)
+    for hd, declared in by_header.items():
+        for n in declared:
+            assert (n in ct.BY_NAME) != (n in ct.EXCLUDED), f"{n}: exported by include/{hd}, " \
+                "needs exactly one of a row in tests/contract_table.py or an entry of EXCLUDED"
     for n, why in ct.EXCLUDED.items():
         assert n in names, f"{n} is excluded but not exported"
         assert len(why) >= 4

@@ -1,4 +1,4 @@
-"""What every entry point of include/mgp.h does to the memory it is handed (tests/contract_table.py has one row per
+"""What every entry point of include/*.h does to the memory it is handed (tests/contract_table.py has one row per
 entry point; tests/buffer_contract.py the guard-banded buffers).
 
 A. every case with all device pointers 16-byte aligned, then all of them one element past a 16-byte boundary: both runs
@@ -389,7 +389,8 @@ def test_conjugate_gradient_facade_behind_unfinished_producers(side, op, Bt):
     assert ct.relerr(sol.cpu().numpy(), o_sol) < 1e-9
 
 
-@pytest.mark.parametrize("name", ["mgp_dot_all", "mgp_k_dense_vjp", "mgp_kxx_grad", "mgp_kmn_knm_vjp"])
+@pytest.mark.parametrize("name", ["mgp_dot_all", "mgp_k_dense_vjp", "mgp_kxx_grad", "mgp_kmn_knm_vjp",
+                                  "mgp_kmn_knm_vjp_anyd"])
 def test_host_scalar_wrappers_behind_unfinished_producers(side, name):
     """the `cggp.ops` wrappers that hand host scalars back: their read-back must wait for the stream the call was
     enqueued on (the process-wide handle follows torch's current stream, `Handle.sync_stream`)"""
@@ -414,6 +415,12 @@ def test_host_scalar_wrappers_behind_unfinished_producers(side, name):
             spec = ops.KernelSpec(c["kind"], ct.VAR, list(ins["_ls"]), c["D"])
             dv, dl = ops.kxx_grad(spec, bufs["X"], bufs["U"], bufs["V"], layout=c["layout"])
             got = dict(dv=dv, dl=np.asarray(dl))
+        elif name == "mgp_kmn_knm_vjp_anyd":  # case 0: D = 33, the staged route (`ops.kmn_knm_vjp` stops at D = 32)
+            assert c["D"] == 33
+            spec = ops.KernelSpec(c["kind"], row.VARIANCE, list(ins["_ls"]), c["D"])
+            dv, dl, dZ = ops.kmn_knm_vjp_anyd(spec, bufs["X"], bufs["Z"], bufs["Gq"], bufs.get("Y"), bufs.get("Gb"),
+                                              need_dZ=True, panel_rows=c["panel_rows"])
+            got = dict(dv=dv, dl=np.asarray(dl), dZ=dZ.clone())
         else:
             spec = ops.KernelSpec(c["kind"], ct.VAR, list(ins["_ls"]), c["D"])
             dv, dl, dZ = ops.kmn_knm_vjp(spec, bufs["X"], bufs["Z"], bufs["Gq"], bufs.get("Y"), bufs.get("Gb"),
