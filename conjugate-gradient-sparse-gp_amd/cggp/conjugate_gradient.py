@@ -211,6 +211,32 @@ def use_fused_variance(fused_variance, dtype, D, M):
     return bool(fused_variance)
 
 
+# `wide_anyd="auto"` takes the many-column form above 32 dimensions (`MGP_OP_KMM_LAMBDA_WIDE_ANYD`,
+# include/mgp_sweep_anyd.h) where it took at most 0.9 of the time of the FASTER of the two existing routes (the plain
+# kind's panels, `MGP_OP_KMM_LAMBDA_ANYD`) at every measured point of a region: fp64,
+# WIDE_ANYD_AUTO_MIN_D <= D <= WIDE_ANYD_AUTO_MAX_D, at least WIDE_ANYD_AUTO_MIN_COLUMNS columns and
+# M >= WIDE_ANYD_AUTO_MIN_M -- M in {2^12, 2^14, 2^16}, D in {33, 77, 90, 128, 512}, 16, 48, 64 and 256 columns, SE and
+# Matern-3/2 (profiles/kmm_wide_anyd_times.json).  None for the column count: no such region, "auto" means
+# False -- measured, new / faster existing route: 0.87 - 3.6 from 48 columns on (0.07 - 0.14 of MGP_OP_KMM_LAMBDA_ANYD at 256
+# columns, but the plain kind's panels are faster still); at or below 0.9 only at 16 columns, and there not everywhere.
+WIDE_ANYD_AUTO_MIN_COLUMNS = None
+WIDE_ANYD_AUTO_MIN_M = 1 << 12
+WIDE_ANYD_AUTO_MIN_D = 33
+WIDE_ANYD_AUTO_MAX_D = 512
+
+
+def check_wide_anyd(wide_anyd, name="wide_anyd"):
+    """`wide_anyd` as given, or `ValueError`: False, True or "auto"."""
+    return check_wide(wide_anyd, name)
+
+
+def wide_anyd_auto(dtype, D, columns, M):
+    """The rule behind `wide_anyd="auto"`."""
+    return (WIDE_ANYD_AUTO_MIN_COLUMNS is not None and dtype == torch.float64
+            and WIDE_ANYD_AUTO_MIN_D <= int(D) <= WIDE_ANYD_AUTO_MAX_D and int(columns) >= WIDE_ANYD_AUTO_MIN_COLUMNS
+            and int(M) >= WIDE_ANYD_AUTO_MIN_M)
+
+
 def anyd_matvec(fused_anyd, which, spec, X, *args, **kwargs):
     """`ops.knm_matvec`, `ops.kmn_matvec` or `ops.kxx_matvec` (`which` = "knm", "kmn", "kxx"; the arguments after `spec`
     are theirs), or its `_anyd` form under the rule of `use_fused_anyd`: the one helper the models route their direct
@@ -231,11 +257,17 @@ class KmmLambdaOperator(LinearOperator):
     iff `wide_auto(dtype, D, columns, M)`, decided per solve or product, where the column count is known.
 
     `fused_anyd` (False, True or "auto"): at D > 32, where `wide` falls back to the sweep, `MGP_OP_KMM_LAMBDA_ANYD` -- the
-    fused any-D sweep instead of kernel panels (fp64; fp32 gives the plain kind's bits).  At D <= 32 `wide` decides."""
+    fused any-D sweep instead of kernel panels (fp64; fp32 gives the plain kind's bits).  At D <= 32 `wide` decides.
 
-    def __init__(self, kernel, Z, lam, wide=False, fused_anyd=False):
+    `wide_anyd` (False, True or "auto"): at D > 32 in fp64, `MGP_OP_KMM_LAMBDA_WIDE_ANYD` -- the many-column form with
+    the distance tiles on the matrix cores, each kernel value evaluated once per 256 right-hand sides and no kernel
+    panel.  It is asked first: True, or "auto" and `wide_anyd_auto(dtype, D, columns, M)`, takes the kind; otherwise,
+    and at D <= 32 or in fp32 always, `fused_anyd` and `wide` decide as above."""
+
+    def __init__(self, kernel, Z, lam, wide=False, fused_anyd=False, wide_anyd=False):
         self.wide = check_wide(wide)
         self.fused_anyd = check_fused_anyd(fused_anyd)
+        self.wide_anyd = check_wide_anyd(wide_anyd)
         self.Z = _hip.check_tensor(Z, "Z")
         self.lam = _hip.check_tensor(lam, "lam", dtype=self.Z.dtype).reshape(-1)
         M = self.Z.shape[0]
@@ -250,6 +282,9 @@ class KmmLambdaOperator(LinearOperator):
     def kind_for(self, columns):
         """The operator kind libmgp is handed for `columns` right-hand sides."""
         D = self.Z.shape[1]
+        if D > WIDE_MAX_D and self.dtype == torch.float64 and self.wide_anyd is not False:
+            if self.wide_anyd is True or wide_anyd_auto(self.dtype, D, max(int(columns), 1), self.shape[0]):
+                return _hip.OP_KMM_LAMBDA_WIDE_ANYD
         if D > WIDE_MAX_D and use_fused_anyd(self.fused_anyd, self.dtype, D, max(int(columns), 1)):
             return _hip.OP_KMM_LAMBDA_ANYD
         wide = self.wide

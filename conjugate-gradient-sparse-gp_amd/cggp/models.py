@@ -308,6 +308,11 @@ class CGGP(ClusterGP):
     K(X*, Z) products: at D > 32 in fp64 libmgp's fused any-D sweeps (include/mgp_sweep_anyd.h) instead of kernel
     panels; "auto" follows `conjugate_gradient.fused_anyd_auto`.
 
+    `wide_anyd` (False, True or "auto"; with `matrix_free=True` only, anything but False without it is a `ValueError`)
+    is the `wide_anyd` argument of every `KmmLambdaOperator` the model makes: at D > 32 in fp64 the many-column form
+    `MGP_OP_KMM_LAMBDA_WIDE_ANYD` (what `wide_solves` is at D <= 32) for `W = CG(K_mm + Lambda, K_mn)`; "auto" follows
+    `conjugate_gradient.wide_anyd_auto`.
+
     `data_term` ("batch", the default and the reference's form, or "trace"; fp64 only) is what `elbo(data)` does with
     the rows of `data`.  "batch" solves `W = CG(K_mm + Lambda, K_mn)` with one column per row to sum the diagonal of
     `K_nm W`.  "trace" takes that sum as a trace, `B variance - tr(A^-1 K_mn K_nm)`, and estimates it with the probes
@@ -325,9 +330,12 @@ class CGGP(ClusterGP):
 
     def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, matrix_free=False,
                  wide_solves=False, data_term="batch", num_bases=1024, num_samples=5, epsilon="matheron",
-                 fused_anyd=False, **kwargs):
+                 fused_anyd=False, wide_anyd=False, **kwargs):
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         self.fused_anyd = check_fused_anyd(fused_anyd)
+        self.wide_anyd = check_wide(wide_anyd, "wide_anyd")
+        if self.wide_anyd is not False and not matrix_free:
+            raise ValueError("wide_anyd needs matrix_free=True: without it there is no operator to widen")
         if self.fused_anyd is not False and not matrix_free:
             raise ValueError("fused_anyd needs matrix_free=True: without it K_mm is a dense matrix and no sweep runs")
         if self.wide_solves is not False and not matrix_free:
@@ -351,7 +359,7 @@ class CGGP(ClusterGP):
         Z = self.inducing_variable.Z
         spec = self.kernel.spec(Z.shape[1])
         op = KmmLambdaOperator(self.kernel, Z, self.diag_variance[:, 0].contiguous(), wide=self.wide_solves,
-                               fused_anyd=self.fused_anyd)
+                               fused_anyd=self.fused_anyd, wide_anyd=self.wide_anyd)
         return None, op, lambda R: anyd_matvec(self.fused_anyd, "knm", spec, Z, Z, R, ops.ROWS, ops.ROWS)
 
     def prior_kl(self, probes=None):  # :293-322

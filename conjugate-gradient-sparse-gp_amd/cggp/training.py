@@ -191,10 +191,11 @@ class _KzzLambdaSolve(torch.autograd.Function):
     dlam = -sum_r Gb o X; when Z needs a gradient, dZ of the same form by `_kzz_bilinear_grads`."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg, wide=False, fused_anyd=False):
+    def forward(ctx, variance, lengthscales, lam, rhs, Z, kind, cg, wide=False, fused_anyd=False, wide_anyd=False):
         from .conjugate_gradient import KmmLambdaOperator, _solve_device
         kern = _frozen_kernel(kind, variance, lengthscales)
-        ctx.op = KmmLambdaOperator(kern, Z, lam.detach().contiguous(), wide=wide, fused_anyd=fused_anyd)
+        ctx.op = KmmLambdaOperator(kern, Z, lam.detach().contiguous(), wide=wide, fused_anyd=fused_anyd,
+                                   wide_anyd=wide_anyd)
         ctx.cfg = cg.config(Z.shape[0])
         ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
         rows = rhs.detach().t().contiguous()
@@ -215,8 +216,8 @@ class _KzzLambdaSolve(torch.autograd.Function):
         else:
             dvar, dls = ops.kxx_grad(op.spec, op.Z, Gb, sol, ops.ROWS)
         gv, gl = _theta_grads(-dvar, [-v for v in dls], ctx.v_shape, ctx.l_shape)
-        grads = (gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), dZ, None, None, None, None)
-        return grads[:len(ctx.needs_input_grad)]  # `wide` and `fused_anyd` are optional in apply()
+        grads = (gv, gl, -(Gb * sol).sum(dim=0), Gb.t().contiguous(), dZ, None, None, None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `wide`, `fused_anyd`, `wide_anyd` are optional in apply()
 
 
 class _KzzLambdaLogdet(torch.autograd.Function):
@@ -226,8 +227,10 @@ class _KzzLambdaLogdet(torch.autograd.Function):
     needs a gradient, dZ of the same form by `_kzz_bilinear_grads`."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg, wide=False, fused_anyd=False):
+    def forward(ctx, variance, lengthscales, lam, solution, probes, Z, kind, cg, wide=False, fused_anyd=False,
+                wide_anyd=False):
         ctx.kind, ctx.cg, ctx.have, ctx.wide, ctx.fused_anyd = kind, cg, solution is not None, wide, fused_anyd
+        ctx.wide_anyd = wide_anyd
         ctx.v_shape, ctx.l_shape = variance.shape, lengthscales.shape
         ctx.theta = (float(variance), lengthscales.detach().clone())
         ctx.save_for_backward(lam.detach(), probes, Z, *((solution,) if ctx.have else ()))
@@ -242,7 +245,8 @@ class _KzzLambdaLogdet(torch.autograd.Function):
             S = ctx.saved_tensors[3]
         else:
             with torch.no_grad():
-                S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous(), wide=ctx.wide, fused_anyd=ctx.fused_anyd),
+                S = ctx.cg(KmmLambdaOperator(kern, Z, lam.contiguous(), wide=ctx.wide, fused_anyd=ctx.fused_anyd,
+                                             wide_anyd=ctx.wide_anyd),
                            probes)
         P = probes.shape[1]
         scale = float(df) / P
@@ -250,8 +254,8 @@ class _KzzLambdaLogdet(torch.autograd.Function):
                                             ctx.needs_input_grad[5])
         gv, gl = _theta_grads(scale * dvar, [scale * v for v in dls], ctx.v_shape, ctx.l_shape)
         grads = (gv, gl, scale * (S * probes).sum(dim=1), None, None, None if dZ is None else scale * dZ, None, None,
-                 None, None)
-        return grads[:len(ctx.needs_input_grad)]  # `wide` and `fused_anyd` are optional in apply()
+                 None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `wide`, `fused_anyd`, `wide_anyd` are optional in apply()
 
 
 PANEL_BYTES = 256 << 20  # the largest row panel of a [B, M] cotangent that `_knm_theta_grads_panels` forms
@@ -409,6 +413,9 @@ class TrainableCGGP:
     `models.CGGP`; the hyper-parameter gradients keep their entry points.
     `wide_solves` (False, True or "auto"; with `matrix_free=True` only) is handed to every `KmmLambdaOperator`, as in
     `models.CGGP`.
+    `wide_anyd` (False, True or "auto"; with `matrix_free=True` only) likewise: at D > 32 in fp64 the solves of
+    `_KzzLambdaSolve` and `_KzzLambdaLogdet` run `MGP_OP_KMM_LAMBDA_WIDE_ANYD` (include/mgp_sweep_anyd.h), always or
+    under `conjugate_gradient.wide_anyd_auto`.
 
     `fused_point_grads` (False, True or "auto"; default False: the code above, bit for bit) is handed to every
     `self.kernel.K(...)` block: with a trainable Z the backward pass of a block is then one `mgp_k_dense_vjp_points` call
@@ -464,9 +471,12 @@ class TrainableCGGP:
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
                  num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
                  wide_solves=False, trainable_inducing=False, data_term="batch", num_bases=1024, num_samples=5,
-                 epsilon="matheron", fused_anyd=False, fused_point_grads=False):
+                 epsilon="matheron", fused_anyd=False, fused_point_grads=False, wide_anyd=False):
         from .conjugate_gradient import check_wide
         self.fused_point_grads = check_fused_point_grads(fused_point_grads)
+        self.wide_anyd = check_wide(wide_anyd, "wide_anyd")
+        if self.wide_anyd is not False and not matrix_free:
+            raise ValueError("wide_anyd needs matrix_free=True: without it there is no operator to widen")
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         if self.wide_solves is not False and not matrix_free:
             raise ValueError("wide_solves needs matrix_free=True: without it there is no operator to widen")
@@ -523,7 +533,8 @@ class TrainableCGGP:
         P = probes.shape[1]
         times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
         wide = self.wide_solves
-        solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
+        solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd,
+                                                          self.wide_anyd)
         if self.fused_solves:
             B = Kmn.shape[1]
             sol = solve(torch.cat([self.pseudo_u, Kmn, probes], dim=1))  # :303, :339, :311 in one solve
@@ -539,10 +550,10 @@ class TrainableCGGP:
             own = rademacher((M, P), dt, dev, self.logdet_probe_seed)  # fresh draw, :38-39
             self.logdet_probe_seed += 1
             logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None, own, Z, kind, cg, wide,
-                                            self.fused_anyd)  # solved in the backward pass
+                                            self.fused_anyd, self.wide_anyd)  # solved in the backward pass
         else:
             logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, S.detach(), probes, Z, kind, cg, wide,
-                                            self.fused_anyd)  # K^-1 Zp reused
+                                            self.fused_anyd, self.wide_anyd)  # K^-1 Zp reused
         const = torch.log(lam).sum()  # :321
         kl = 0.5 * (quad - trace + logdet - const)
         scale = 1.0 if self.num_data is None else float(self.num_data) / float(x.shape[0])  # :163-169
@@ -579,7 +590,7 @@ class TrainableCGGP:
         if self.matrix_free:  # solved in the backward pass from `own`, else K^-1 Zp reused
             logdet = _KzzLambdaLogdet.apply(var_p, ls, lam, None if own is not None else S.detach(),
                                             probes if own is None else own, Z, kind, cg, self.wide_solves,
-                                            self.fused_anyd)
+                                            self.fused_anyd, self.wide_anyd)
         elif own is not None:
             logdet = eval_logdet(KL, cg, P, own)  # second probe solve in the backward pass, :40-42
         else:
@@ -604,7 +615,8 @@ class TrainableCGGP:
         if self.matrix_free:
             wide = self.wide_solves
             times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
-            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
+            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd,
+                                                          self.wide_anyd)
         else:
             Kmm = self.kernel.K(Z, fused_point_grads=self.fused_point_grads)  # :300 / :333
             KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
@@ -664,7 +676,8 @@ class TrainableCGGP:
         if self.matrix_free:
             wide = self.wide_solves
             times_kzz = lambda V: _KzzTimes.apply(var_p, ls, Z, V, kind, self.fused_anyd)
-            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd)
+            solve = lambda rhs: _KzzLambdaSolve.apply(var_p, ls, lam, rhs, Z, kind, cg, wide, self.fused_anyd,
+                                                          self.wide_anyd)
         else:
             Kmm = self.kernel.K(Z, fused_point_grads=self.fused_point_grads)  # :300 / :333
             KL = Kmm + torch.diag(lam)  # add_diagonal, :301 / :337
@@ -762,7 +775,7 @@ class TrainableCGGP:
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
                     num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves,
                     data_term=self.data_term, num_bases=self.num_bases, num_samples=self.num_samples,
-                    epsilon=self.epsilon, fused_anyd=self.fused_anyd)
+                    epsilon=self.epsilon, fused_anyd=self.fused_anyd, wide_anyd=self.wide_anyd)
 
 
 class _GPRLmlEstimate(torch.autograd.Function):

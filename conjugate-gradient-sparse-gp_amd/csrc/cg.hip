@@ -414,6 +414,10 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
   switch (op->kind) {
     case MGP_OP_DENSE:
       return mgp_symm_matmul_gated(h, op->dtype, op->A, n, P, Bt, out, gate, loc);
+    case MGP_OP_KMM_LAMBDA_WIDE_ANYD:  // the many-column form above 32 dimensions (kmm_wide_anyd.hip); else as the next kind
+      if (mgp_kmm_wide_anyd_serves(op->kernel))
+        return mgp_kmm_wide_anyd_apply(h, op->kernel, op->Z, op->M, op->lambda, P, Bt, out, gate);
+      [[fallthrough]];
     case MGP_OP_KMM_LAMBDA_WIDE:  // the many-column form (project.hip); fp32 and D > 32 take the sweep form below
       if (mgp_kmm_wide_serves(op->kernel))
         return mgp_kmm_wide_apply(h, op->kernel, op->Z, op->M, op->lambda, P, Bt, out, gate);
@@ -540,7 +544,7 @@ int check_operator(mgp_handle* h, const mgp_operator* op) {
   if (op->kind == MGP_OP_DENSE) {
     if (!op->A) return mgp_fail(h, MGP_E_BADARG, "dense operator without matrix");
   } else if (sgpr || op->kind == MGP_OP_KMM_LAMBDA || op->kind == MGP_OP_KMM_LAMBDA_WIDE ||
-             op->kind == MGP_OP_KMM_LAMBDA_ANYD) {
+             op->kind == MGP_OP_KMM_LAMBDA_ANYD || op->kind == MGP_OP_KMM_LAMBDA_WIDE_ANYD) {
     MGP_TRY(mgp_check_kernel(h, op->kernel));
     if (op->kernel->dtype != op->dtype) return mgp_fail(h, MGP_E_DTYPE, "operator/kernel dtype mismatch");
     if (op->M != op->n || !op->Z) return mgp_fail(h, MGP_E_SHAPE, "operator needs Z with M == n");
@@ -893,7 +897,11 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
                 /*pre=*/pc, /*a=*/arena, /*z=*/pc.cb ? (T*)pc.cb->cb_z : arena.z, /*dense1=*/dense1, /*fused=*/fused};
   // many-column (K_mm + Lambda): the arena for the widest group and the pack of Z before the loop, nothing inside it
   WideHold wide_hold(h);
-  if (op->kind == MGP_OP_KMM_LAMBDA_WIDE && mgp_kmm_wide_serves(op->kernel)) {
+  if (op->kind == MGP_OP_KMM_LAMBDA_WIDE_ANYD && mgp_kmm_wide_anyd_serves(op->kernel)) {
+    MGP_TRY(mgp_kmm_wide_anyd_prepare(h, op->kernel, op->Z, op->M, Bt, nullptr));
+    wide_hold.hold(op->Z, op->M);
+  } else if ((op->kind == MGP_OP_KMM_LAMBDA_WIDE || op->kind == MGP_OP_KMM_LAMBDA_WIDE_ANYD) &&
+             mgp_kmm_wide_serves(op->kernel)) {
     MGP_TRY(mgp_kmm_wide_prepare(h, op->kernel, op->Z, op->M, Bt, nullptr));
     wide_hold.hold(op->Z, op->M);
   }

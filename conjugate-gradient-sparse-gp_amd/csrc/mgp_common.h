@@ -165,7 +165,7 @@ struct PackHold {
   }
 };
 
-// scope guard of mgp_pcg_solve on MGP_OP_KMM_LAMBDA_WIDE: Z is packed once, before the loop, and held until the solve ends
+// scope guard of mgp_pcg_solve on MGP_OP_KMM_LAMBDA_WIDE and MGP_OP_KMM_LAMBDA_WIDE_ANYD: Z is packed once, before the loop, and held until the solve ends
 struct WideHold {
   mgp_handle* h;
   explicit WideHold(mgp_handle* hh) : h(hh) { release(); }
@@ -431,6 +431,13 @@ bool mgp_kmm_wide_serves(const mgp_kernel* k);
 int mgp_kmm_wide_prepare(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, int64_t Bt, const int* gate);
 int mgp_kmm_wide_apply(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, const void* lambda, const void* P,
                        int64_t Bt, void* out, const int* gate);
+// kmm_wide_anyd.hip (MGP_OP_KMM_LAMBDA_WIDE_ANYD, include/mgp_sweep_anyd.h): the same operator and the same
+// prepare / apply / WideHold protocol at fp64 and D > MGP_FUSED_MAX_D (mgp_kmm_wide_anyd_serves), the distance tiles on
+// the matrix cores with K in slices
+bool mgp_kmm_wide_anyd_serves(const mgp_kernel* k);
+int mgp_kmm_wide_anyd_prepare(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, int64_t Bt, const int* gate);
+int mgp_kmm_wide_anyd_apply(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, const void* lambda,
+                            const void* P, int64_t Bt, void* out, const int* gate);
 // generic-D forms (generic.hip): explicit panels + NT GEMM, any D <= MGP_MAX_D
 int mgp_k_dense_generic(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
                         void* out, int64_t ld, double jitter, const void* diag_add, const int* gate);
