@@ -18,6 +18,7 @@ MGP_COMM_ID_BYTES = 128
 F32, F64 = 0, 1
 SE, MATERN12, MATERN32, MATERN52 = 0, 1, 2, 3
 COLS, ROWS = 0, 1
+RFF_ANYD = 16  # MGP_RFF_ANYD (include/mgp_pathwise.h): OR into the layout word of mgp_rff_sample / mgp_rff_sample_vjp
 PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK, PRE_LOWRANK, PRE_LOWRANK_WIDE = 0, 1, 2, 3, 4, 5, 6
 OP_DENSE, OP_SGPR, OP_KMM_LAMBDA, OP_KXX_NOISE, OP_KMM_LAMBDA_WIDE = 0, 1, 2, 3, 4
 OP_SGPR_ANYD, OP_KMM_LAMBDA_ANYD, OP_KXX_NOISE_ANYD = 5, 6, 7  # include/mgp_sweep_anyd.h

@@ -326,11 +326,20 @@ class CGGP(ClusterGP):
     never negative in its quadratic part, and with `epsilon="matheron"` (the default here; "reference" as in
     `pathwise_epsilon`) its expectation is the "batch" data term up to the random-feature truncation.  The draws come
     from `pathwise_seed`, which advances per call, or are injected as `elbo(data, pathwise=(E, W, xi))`
-    (`draw_pathwise`).  Value only: `training.TrainableCGGP` is the differentiable form."""
+    (`draw_pathwise`).  Value only: `training.TrainableCGGP` is the differentiable form.
+
+    `rff_anyd` (False, True or "auto"; with `data_term="pathwise"` only, anything but False with another data term is a
+    `ValueError`): the prior draw at D > 32 in fp64 by libmgp's fused any-D kernels (MGP_RFF_ANYD,
+    include/mgp_pathwise.h) instead of feature panels; "auto" follows `rff.rff_anyd_auto`."""
 
     def __init__(self, kernel, likelihood, inducing_variable, conjugate_gradient, num_probes=5, matrix_free=False,
                  wide_solves=False, data_term="batch", num_bases=1024, num_samples=5, epsilon="matheron",
-                 fused_anyd=False, wide_anyd=False, **kwargs):
+                 fused_anyd=False, wide_anyd=False, rff_anyd=False, **kwargs):
+        from .rff import check_rff_anyd
+        self.rff_anyd = check_rff_anyd(rff_anyd)
+        if self.rff_anyd is not False and data_term != "pathwise":
+            raise ValueError(f"rff_anyd needs data_term='pathwise': no other data term draws random Fourier features "
+                             f"(got data_term={data_term!r})")
         self.wide_solves = check_wide(wide_solves, "wide_solves")
         self.fused_anyd = check_fused_anyd(fused_anyd)
         self.wide_anyd = check_wide(wide_anyd, "wide_anyd")
@@ -519,7 +528,8 @@ class CGGP(ClusterGP):
         S, L = W.shape[0], E.shape[0]
         ls = torch.tensor(kernel.spec(D).lengthscales, dtype=Z.dtype, device=Z.device)
         theta = (E / ls[None, :]).contiguous()
-        prior = rff.rff_sample(torch.cat([x, Z], dim=0), kernel, L, S, theta=theta, weights=W)  # [S, B + M]
+        prior = rff.rff_sample(torch.cat([x, Z], dim=0), kernel, L, S, theta=theta, weights=W,
+                               rff_anyd=self.rff_anyd)  # [S, B + M]
         lam = self.diag_variance[:, 0]
         eps = pathwise_epsilon(lam, S, self.epsilon, xi=xi)
         rhs = (self.pseudo_u[:, 0][None, :] - prior[:, B:] - eps).t().contiguous()  # [M, S]
@@ -613,10 +623,15 @@ class PathwiseClusterGP(ClusterGP):
 
     Random draws: numpy PCG64 from `seed` -- theta, then W, then the [S, M] normals of eps.  The values are not
     differentiable: like the reference, which only evaluates this model, `elbo` returns a float and no gradient
-    flows through the random-feature term."""
+    flows through the random-feature term.
+
+    `rff_anyd` (False, True or "auto"): the prior draw at D > 32 in fp64 by libmgp's fused any-D kernels
+    (MGP_RFF_ANYD, include/mgp_pathwise.h) instead of feature panels; "auto" follows `rff.rff_anyd_auto`."""
 
     def __init__(self, kernel, likelihood, inducing_variable, *, conjugate_gradient=None, epsilon="reference",
-                 **kwargs):
+                 rff_anyd=False, **kwargs):
+        from .rff import check_rff_anyd
+        self.rff_anyd = check_rff_anyd(rff_anyd)
         super().__init__(kernel, likelihood, inducing_variable, **kwargs)
         if epsilon not in EPSILON_CONVENTIONS:
             raise ValueError(f"epsilon must be one of {EPSILON_CONVENTIONS}, got {epsilon!r}")
@@ -654,7 +669,8 @@ class PathwiseClusterGP(ClusterGP):
         if weights is None:
             weights = rff.rff_weights(num_samples, num_bases, rng)
         prior_at = torch.cat([sample_at, Z], dim=0)  # :397
-        prior = rff.rff_sample(prior_at, kernel, num_bases, num_samples, theta=theta, weights=weights)  # [S, N + M]
+        prior = rff.rff_sample(prior_at, kernel, num_bases, num_samples, theta=theta, weights=weights,
+                               rff_anyd=self.rff_anyd)  # [S, N + M]
         prior_fx, prior_fz = prior[:, :n], prior[:, n:]
         epsilon = pathwise_epsilon(lambda_diag, num_samples, self.epsilon, rng, xi)  # :404-408
         solve_against = self.pseudo_u[:, 0][None, :] - prior_fz - epsilon  # [S, M], :414

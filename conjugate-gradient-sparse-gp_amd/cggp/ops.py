@@ -589,9 +589,11 @@ def rff_features(X, theta):
     return out
 
 
-def rff_sample(X, theta, W, scale, out_layout=ROWS):
+def rff_sample(X, theta, W, scale, out_layout=ROWS, anyd=False):
     """scale * W [S, 2L] @ Phi(X)^T without forming Phi where D <= 32 and S <= 8 (`rff_sample`, reference
-    `cggp/rff.py:60-73`).  out [S, N] (ROWS) or [N, S] (COLS)."""
+    `cggp/rff.py:60-73`).  out [S, N] (ROWS) or [N, S] (COLS).  `anyd=True` ORs `MGP_RFF_ANYD` into the layout word:
+    fp64, D > 32 and S <= 8 then take the fused any-D kernels of csrc/rff_anyd.hip instead of feature panels;
+    anything else is the plain call."""
     X = _points(X, "X")
     theta = _points(theta, "theta", X.shape[1], X.dtype)
     N, D = X.shape
@@ -608,14 +610,15 @@ def rff_sample(X, theta, W, scale, out_layout=ROWS):
     # L == 0 goes through the C-ABI too: libmgp writes the zeros
     hd = _hip.get_handle(X.device)
     hd.check(hd.lib.mgp_rff_sample(hd.h, _hip.dtype_code(X), _hip.ptr(X), N, D, _hip.ptr(theta), L, _hip.ptr(W), S,
-                                   float(scale), _hip.ptr(out), out_layout))
+                                   float(scale), _hip.ptr(out), out_layout | (_hip.RFF_ANYD if anyd else 0)))
     return out
 
 
-def rff_sample_vjp(X, theta, W, scale, G, g_layout=ROWS, want_dtheta=True, want_dX=False):
+def rff_sample_vjp(X, theta, W, scale, G, g_layout=ROWS, want_dtheta=True, want_dX=False, anyd=False):
     """Backward pass of `rff_sample` at the cotangent G [S, N] (ROWS) or [N, S] (COLS): (dtheta [L, D] or None,
     dX [N, D] or None) by `mgp_rff_sample_vjp` (include/mgp_pathwise.h), phases as in the forward pass.  fp64,
-    D <= 32 and 1 <= S <= 8 only: libmgp refuses anything else (MgpError).  The derivative in `scale` is
+    D <= 32 and 1 <= S <= 8 only: libmgp refuses anything else (MgpError).  `anyd=True` ORs `MGP_RFF_ANYD` into the
+    layout word, which opens 32 < D <= 512 (csrc/rff_anyd.hip) and changes nothing else.  The derivative in `scale` is
     sum(G o out) / scale and needs no call."""
     X = _points(X, "X")
     theta = _points(theta, "theta", X.shape[1], X.dtype)
@@ -636,5 +639,6 @@ def rff_sample_vjp(X, theta, W, scale, G, g_layout=ROWS, want_dtheta=True, want_
         return dtheta, dX  # no element to write; N == 0 or L == 0 with one goes through the C-ABI: libmgp writes the zeros
     hd =_hip.get_handle(X.device)
     hd.check(hd.lib.mgp_rff_sample_vjp(hd.h, _hip.dtype_code(X), _hip.ptr(X), N, D, _hip.ptr(theta), L, _hip.ptr(W), S,
-                                       float(scale), _hip.ptr(G), g_layout, _hip.ptr(dtheta), _hip.ptr(dX)))
+                                       float(scale), _hip.ptr(G), g_layout | (_hip.RFF_ANYD if anyd else 0),
+                                       _hip.ptr(dtheta), _hip.ptr(dX)))
     return dtheta, dX

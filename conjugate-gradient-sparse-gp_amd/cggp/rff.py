@@ -21,6 +21,44 @@ from . import ops
 _SMOOTHNESS = {"matern12": 1, "matern32": 3, "matern52": 5}
 
 
+# `rff_anyd="auto"` takes the fused any-D kernels (MGP_RFF_ANYD, include/mgp_pathwise.h) in a region (op, S,
+# D <= max_d, N L >= min_nl) only where they took at most 0.9 of the parent route's time (feature panels and a GEMM
+# forward, `training._rff_vjp_panels` backward) at EVERY measured point of that region; `tools/run_rff_anyd.py
+# --derive` computes the table from profiles/rff_anyd_times.json and tests/test_rff_anyd_abi.py pins it to that file.
+# Measured: D in {33, 48, 77, 90, 128, 256, 257, 512}, S in {1, 5, 8}, L in {256, 1024, 4096}, N in {2^14, 2^17, 2^20}
+# (DESIGN 4.24).  Forward: 0.10 - 0.65 everywhere.  dtheta and dX: 0.02 - 0.82 up to D = 257; at D = 512, where the
+# output dimensions go in two groups and the phases are formed twice, 0.35 - 0.93 at L <= 1024 and 1.10 - 1.43 at
+# L = 4096, so D = 512 is left out.  2^22 = 2^14 * 256 is the smallest N L measured.
+# {(op, S): (max_d, min_nl)}; a sample count or an operation that was not measured is not taken.
+RFF_ANYD_AUTO_MIN_D = 33
+RFF_ANYD_AUTO = {(op, S): (max_d, 1 << 22)
+                 for op, max_d in (("forward", 512), ("dtheta", 257), ("dX", 257)) for S in (1, 5, 8)}
+RFF_ANYD_MAX_S = 8  # above it libmgp's flagged calls are the plain ones
+
+
+def check_rff_anyd(rff_anyd, name="rff_anyd"):
+    """`rff_anyd` as given, or `ValueError`: False, True or "auto"."""
+    if isinstance(rff_anyd, bool) or (isinstance(rff_anyd, str) and rff_anyd == "auto"):
+        return rff_anyd
+    raise ValueError(f"{name} must be False, True or 'auto', got {rff_anyd!r}")
+
+
+def rff_anyd_auto(dtype, D, S, N, L, op="forward"):
+    """The rule behind `rff_anyd="auto"` for `op` ("forward", "dtheta" or "dX"): fp64, a measured sample count, and
+    RFF_ANYD_AUTO_MIN_D <= D <= max_d, N L >= min_nl of RFF_ANYD_AUTO[(op, S)]."""
+    region = RFF_ANYD_AUTO.get((op, int(S)))
+    return (dtype == torch.float64 and region is not None and RFF_ANYD_AUTO_MIN_D <= int(D) <= region[0]
+            and int(N) * int(L) >= region[1])
+
+
+def use_rff_anyd(rff_anyd, dtype, D, S, N, L, op="forward"):
+    """Whether a call with this setting ORs the flag in.  True: wherever libmgp serves it (fp64, D > 32, S <= 8; the
+    flag changes nothing elsewhere, but the backward pass must not be sent where the plain call refuses)."""
+    if rff_anyd == "auto":
+        return rff_anyd_auto(dtype, D, S, N, L, op)
+    return bool(rff_anyd) and dtype == torch.float64 and int(D) > 32 and 1 <= int(S) <= RFF_ANYD_MAX_S
+
+
 def _rng(seed):
     # an int / None seeds a fresh PCG64 stream; a Generator continues the caller's
     return np.random.default_rng(seed)
@@ -66,11 +104,13 @@ def rff_weights(num_samples, num_bases, seed=None):
     return torch.from_numpy(_rng(seed).standard_normal((int(num_samples), 2 * int(num_bases))))
 
 
-def rff_sample(inputs, kernel, num_bases, num_samples=1, *, seed=None, theta=None, weights=None):
+def rff_sample(inputs, kernel, num_bases, num_samples=1, *, seed=None, theta=None, weights=None, rff_anyd=False):
     """[S, N] prior function samples sqrt(variance / L) * W Phi(inputs)^T (reference `rff.py:60-73`).
 
     One stream: theta first (unless injected), then the weights (unless injected).  On the device the samples are
-    formed by `mgp_rff_sample` without the [N, 2L] feature panel where D <= 32 and S <= 8."""
+    formed by `mgp_rff_sample` without the [N, 2L] feature panel where D <= 32 and S <= 8 -- and, with `rff_anyd`
+    (False, True or "auto": `rff_anyd_auto`), at 32 < D <= 512 in fp64 too (csrc/rff_anyd.hip)."""
+    check_rff_anyd(rff_anyd)
     D = inputs.shape[-1]
     rng = _rng(seed)
     if theta is None:
@@ -84,5 +124,6 @@ def rff_sample(inputs, kernel, num_bases, num_samples=1, *, seed=None, theta=Non
         raise ValueError(f"weights must be [S, 2L={2 * L}], got {tuple(weights.shape)}")
     scale = math.sqrt(kernel.variance / L) if L > 0 else 0.0
     if inputs.is_cuda:
-        return ops.rff_sample(inputs.contiguous(), theta, weights, scale, ops.ROWS)
+        anyd = use_rff_anyd(rff_anyd, inputs.dtype, D, weights.shape[0], inputs.shape[0], L)
+        return ops.rff_sample(inputs.contiguous(), theta, weights, scale, ops.ROWS, anyd=anyd)
     return scale * (weights @ basis_vectors(inputs, theta).t())

@@ -337,14 +337,19 @@ class _RffSample(torch.autograd.Function):
     frequencies theta [L, D], in scale (a 0-dim tensor, sqrt(variance / L)) and in Z.  Forward: ONE `mgp_rff_sample` on
     the B + M rows.  Backward at G [S, B + M]: dtheta from one `mgp_rff_sample_vjp` call on all rows, dZ from a second
     call on the M rows of Z alone (only when Z needs a gradient), dscale = sum(G o out) / scale by `mgp_dot_all`.
-    D > 32 or S > 8 (which that entry point refuses): `_rff_vjp_panels`."""
+    D > 32 or S > 8 (which that entry point refuses): `_rff_vjp_panels` -- unless `rff_anyd` (False, True or "auto", as
+    `rff.rff_sample`) sends the D > 32, S <= 8 calls to the fused any-D kernels (MGP_RFF_ANYD)."""
 
     @staticmethod
-    def forward(ctx, theta, scale, x, Z, W):
+    def forward(ctx, theta, scale, x, Z, W, rff_anyd=False):
+        from . import rff
         pts = torch.cat([x, Z.detach()], dim=0).contiguous()
         theta, W = theta.detach().contiguous(), W.contiguous()
         ctx.scale, ctx.B = float(scale), x.shape[0]
-        out = ops.rff_sample(pts, theta, W, ctx.scale, ops.ROWS)
+        ctx.rff_anyd = rff.check_rff_anyd(rff_anyd)
+        anyd = pts.is_cuda and rff.use_rff_anyd(rff_anyd, pts.dtype, pts.shape[1], W.shape[0], pts.shape[0],
+                                                theta.shape[0])
+        out = ops.rff_sample(pts, theta, W, ctx.scale, ops.ROWS, anyd=anyd)
         ctx.save_for_backward(pts, theta, W, out, scale)
         return out
 
@@ -353,24 +358,28 @@ class _RffSample(torch.autograd.Function):
         pts, theta, W, out, scale = ctx.saved_tensors
         G = G.contiguous()
         D, S, B = pts.shape[1], W.shape[0], ctx.B
+        from . import rff
         fused = D <= 32 and S <= 8
+        L = theta.shape[0]
+        anyd = lambda n, op: pts.is_cuda and rff.use_rff_anyd(ctx.rff_anyd, pts.dtype, D, S, n, L, op)
         need_theta, need_scale, need_z = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
         dtheta = dZ = dscale = None
         if need_theta:
-            if fused:
-                dtheta, _ = ops.rff_sample_vjp(pts, theta, W, ctx.scale, G, ops.ROWS)
+            if fused or anyd(pts.shape[0], "dtheta"):
+                dtheta, _ = ops.rff_sample_vjp(pts, theta, W, ctx.scale, G, ops.ROWS, anyd=not fused)
             else:
                 dtheta, _ = _rff_vjp_panels(pts, theta, W, ctx.scale, G)
         if need_z:
-            Zd, Gz = pts[B:], G[:, B:].contiguous()
-            if fused:
-                _, dZ = ops.rff_sample_vjp(Zd, theta, W, ctx.scale, Gz, ops.ROWS, want_dtheta=False, want_dX=True)
+            Zd, Gz = pts[B:].contiguous(), G[:, B:].contiguous()
+            if fused or anyd(Zd.shape[0], "dX"):
+                _, dZ = ops.rff_sample_vjp(Zd, theta, W, ctx.scale, Gz, ops.ROWS, want_dtheta=False, want_dX=True,
+                                           anyd=not fused)
             else:
                 _, dZ = _rff_vjp_panels(Zd, theta, W, ctx.scale, Gz, want_dX=True)
         if need_scale:
             v = ops.dot_all(G, out) / ctx.scale if ctx.scale != 0.0 else 0.0
             dscale = torch.tensor(v, dtype=scale.dtype, device=scale.device).reshape(scale.shape)
-        return dtheta, dscale, None, dZ, None
+        return (dtheta, dscale, None, dZ, None, None)[:len(ctx.needs_input_grad)]  # `rff_anyd` is optional in apply()
 
 
 class _KmnKnm(torch.autograd.Function):
@@ -466,13 +475,21 @@ class TrainableCGGP:
     other forms; `fused_solves=True` sends [pseudo_u | probes | u - f_Z - eps] through one solve.  The draws (E, W, xi)
     come from `pathwise_seed`, which advances per call like `probe_seed`, or are injected as
     `elbo(data, pathwise=(E, W, xi))` (`draw_pathwise`).  fp64 only; D > 32 or S > 8: the prior draw's backward pass walks
-    row chunks of feature panels (`_rff_vjp_panels`), and `trainable_inducing=True` at D > 32 is a `ValueError`."""
+    row chunks of feature panels (`_rff_vjp_panels`), and `trainable_inducing=True` at D > 32 is a `ValueError`.
+    `rff_anyd` (False, True or "auto"; with `data_term="pathwise"` only, anything but False with another data term is a
+    `ValueError`) sends the prior draw and its backward pass at D > 32, S <= 8 to libmgp's fused any-D kernels
+    (MGP_RFF_ANYD, include/mgp_pathwise.h) instead; "auto" follows `rff.rff_anyd_auto`."""
 
     def __init__(self, kernel, noise_variance, Z, conjugate_gradient=None, num_probes=5, *, pseudo_u, cluster_counts,
                  num_data=None, fused_solves=False, independent_logdet_probes=False, matrix_free=False,
                  wide_solves=False, trainable_inducing=False, data_term="batch", num_bases=1024, num_samples=5,
-                 epsilon="matheron", fused_anyd=False, fused_point_grads=False, wide_anyd=False):
+                 epsilon="matheron", fused_anyd=False, fused_point_grads=False, wide_anyd=False, rff_anyd=False):
         from .conjugate_gradient import check_wide
+        from .rff import check_rff_anyd
+        self.rff_anyd = check_rff_anyd(rff_anyd)
+        if self.rff_anyd is not False and data_term != "pathwise":
+            raise ValueError(f"rff_anyd needs data_term='pathwise': no other data term draws random Fourier features "
+                             f"(got data_term={data_term!r})")
         self.fused_point_grads = check_fused_point_grads(fused_point_grads)
         self.wide_anyd = check_wide(wide_anyd, "wide_anyd")
         if self.wide_anyd is not False and not matrix_free:
@@ -686,7 +703,8 @@ class TrainableCGGP:
         rhs = None
         if B > 0:
             theta = E / ls.to(device=dev, dtype=dt)[None, :]  # the reparameterised frequencies, reference rff.py:20-45
-            prior = _RffSample.apply(theta, torch.sqrt(var_p / L), x.contiguous(), Z, W)  # [S, B + M], :397-402
+            prior = _RffSample.apply(theta, torch.sqrt(var_p / L), x.contiguous(), Z, W,
+                                     self.rff_anyd)  # [S, B + M], :397-402
             eps = (torch.sqrt(lam) if self.epsilon == "matheron" else lam)[None, :] * xi  # :404-408
             rhs = (self.pseudo_u[:, 0][None, :] - prior[:, B:] - eps).t()  # [M, S], :414
         if exact:  # the dense model alone
@@ -775,7 +793,8 @@ class TrainableCGGP:
                     num_probes=self.num_probes, pseudo_u=self.pseudo_u, cluster_counts=self.cluster_counts,
                     num_data=self.num_data, matrix_free=self.matrix_free, wide_solves=self.wide_solves,
                     data_term=self.data_term, num_bases=self.num_bases, num_samples=self.num_samples,
-                    epsilon=self.epsilon, fused_anyd=self.fused_anyd, wide_anyd=self.wide_anyd)
+                    epsilon=self.epsilon, fused_anyd=self.fused_anyd, wide_anyd=self.wide_anyd,
+                    rff_anyd=self.rff_anyd)
 
 
 class _GPRLmlEstimate(torch.autograd.Function):

@@ -438,6 +438,13 @@ bool mgp_kmm_wide_anyd_serves(const mgp_kernel* k);
 int mgp_kmm_wide_anyd_prepare(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, int64_t Bt, const int* gate);
 int mgp_kmm_wide_anyd_apply(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, const void* lambda,
                             const void* P, int64_t Bt, void* out, const int* gate);
+// rff_anyd.hip (MGP_RFF_ANYD, include/mgp_pathwise.h): the fused prior sample and its backward pass at fp64,
+// MGP_FUSED_MAX_D < D <= MGP_MAX_D and 1 <= S <= 8 (mgp_rff_anyd_serves), on arguments rff.hip / rff_grad.hip have checked
+bool mgp_rff_anyd_serves(int dtype, int D, int S);
+int mgp_rff_anyd_sample(mgp_handle* h, const double* X, long N, int D, const double* theta, long L, const double* W,
+                        int S, double scale, double* out, int layout);
+int mgp_rff_anyd_vjp(mgp_handle* h, const double* X, long N, int D, const double* theta, long L, const double* W, int S,
+                     double scale, const double* G, long g_sn, long g_ss, double* dtheta, double* dX);
 // generic-D forms (generic.hip): explicit panels + NT GEMM, any D <= MGP_MAX_D
 int mgp_k_dense_generic(mgp_handle* h, const mgp_kernel* k, const void* A, int64_t na, const void* B, int64_t nb,
                         void* out, int64_t ld, double jitter, const void* diag_add, const int* gate);

@@ -12,9 +12,11 @@
 //    wave-uniformly, S accumulators per row, `scale` applied at the end.  When N leaves CUs idle the bases are split
 //    over blockIdx.y into per-chunk partials that rff_reduce_kernel sums in chunk order (deterministic, no atomics).
 //  - panel (S > 8 or D > 32): Phi written in row chunks of at most ~256 MB and multiplied against W by mgp_gemm_nt,
-//    as generic.hip does for the kernel panels.
+//    as generic.hip does for the kernel panels;
+//  - MGP_RFF_ANYD in out_layout, fp64, D > 32, S <= 8: rff_anyd.hip, fused on the matrix cores.
 #include <cstdlib>
 
+#include "../../include/mgp_pathwise.h"
 #include "mgp_common.h"
 #include "rff_math.h"
 
@@ -303,6 +305,8 @@ extern "C" int mgp_rff_sample(mgp_handle* h, int dtype, const void* X, int64_t N
                               int64_t L, const void* W, int32_t S, double scale, void* out, int out_layout) {
   MGP_TRY(rff_check(h, dtype, X, N, D, theta, L));
   if (S < 1) return mgp_fail(h, MGP_E_SHAPE, "rff_sample: S=%d < 1", S);
+  const bool anyd = (out_layout & MGP_RFF_ANYD) != 0;  // the flag only picks the route; the layout is checked without it
+  out_layout &= ~MGP_RFF_ANYD;
   if (out_layout != MGP_COLS && out_layout != MGP_ROWS)
     return mgp_fail(h, MGP_E_BADARG, "rff_sample: bad out_layout %d", out_layout);
   if (!(scale == scale) || scale - scale != 0.0) return mgp_fail(h, MGP_E_BADARG, "rff_sample: scale not finite");
@@ -313,6 +317,9 @@ extern "C" int mgp_rff_sample(mgp_handle* h, int dtype, const void* X, int64_t N
     return MGP_OK;
   }
   if (!W) return mgp_fail(h, MGP_E_BADARG, "rff_sample: NULL W");
+  if (anyd && mgp_rff_anyd_serves(dtype, D, S))
+    return mgp_rff_anyd_sample(h, (const double*)X, N, D, (const double*)theta, L, (const double*)W, S, scale,
+                               (double*)out, out_layout);
   const bool fused = rff_use_fused(D, S);
   return mgp_with_dtype(dtype, [&](auto t) {
     using T = decltype(t);

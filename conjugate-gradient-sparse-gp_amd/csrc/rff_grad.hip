@@ -222,8 +222,10 @@ extern "C" int mgp_rff_sample_vjp(mgp_handle* h, int dtype, const void* X, int64
   if (!h) return MGP_E_BADARG;
   if (dtype != MGP_F64) return mgp_fail(h, MGP_E_DTYPE, "rff_sample_vjp: fp64 only, got dtype %d", dtype);
   if (N < 0 || L < 0) return mgp_fail(h, MGP_E_SHAPE, "rff_sample_vjp: negative size N=%ld L=%ld", (long)N, (long)L);
-  if (D < 1 || D > MGP_FUSED_MAX_D)
-    return mgp_fail(h, MGP_E_BADARG, "rff_sample_vjp: D = %d outside [1, %d]", D, MGP_FUSED_MAX_D);
+  const bool anyd = (g_layout & MGP_RFF_ANYD) != 0;  // the flag only picks the route; the layout is checked without it
+  g_layout &= ~MGP_RFF_ANYD;
+  const int max_d = anyd ? MGP_MAX_D : MGP_FUSED_MAX_D;  // above MGP_FUSED_MAX_D: rff_anyd.hip
+  if (D < 1 || D > max_d) return mgp_fail(h, MGP_E_BADARG, "rff_sample_vjp: D = %d outside [1, %d]", D, max_d);
   if (S < 1 || S > kVjpMaxS) return mgp_fail(h, MGP_E_BADARG, "rff_sample_vjp: S = %d outside [1, %d]", S, kVjpMaxS);
   if (g_layout != MGP_COLS && g_layout != MGP_ROWS)
     return mgp_fail(h, MGP_E_BADARG, "rff_sample_vjp: bad g_layout %d", g_layout);
@@ -236,6 +238,9 @@ extern "C" int mgp_rff_sample_vjp(mgp_handle* h, int dtype, const void* X, int64
   }
   if (!X || !theta || !W || !G) return mgp_fail(h, MGP_E_BADARG, "rff_sample_vjp: NULL data pointer");
   const long g_sn = g_layout == MGP_COLS ? S : 1, g_ss = g_layout == MGP_COLS ? 1 : N;
+  if (D > MGP_FUSED_MAX_D)
+    return mgp_rff_anyd_vjp(h, (const double*)X, N, D, (const double*)theta, L, (const double*)W, S, scale,
+                            (const double*)G, g_sn, g_ss, (double*)dtheta, (double*)dX);
   return mgp_with_dp<4>(D, [&](auto dp) {
     return vjp_dispatch_s<decltype(dp)::value>(h, (const double*)X, N, D, (const double*)theta, L, (const double*)W, S,
                                                scale, (const double*)G, g_sn, g_ss, (double*)dtheta, (double*)dX);

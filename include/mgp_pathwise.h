@@ -50,6 +50,61 @@ int mgp_rff_sample_vjp(mgp_handle* h, int dtype, const void* X, int64_t N, int32
                        const void* W, int32_t S, double scale, const void* G, int g_layout,
                        void* dtheta /* or NULL */, void* dX /* or NULL */);
 
+/* MGP_RFF_ANYD: OR into out_layout of mgp_rff_sample or g_layout of mgp_rff_sample_vjp (csrc/rff_anyd.hip).  The flag
+ * is stripped and the layout word checked as without it (any other bit: MGP_E_BADARG).  With the flag, fp64,
+ * MGP_FUSED_MAX_D < D <= MGP_MAX_D and 1 <= S <= 8, the call takes the fused any-D route below: no [N, 2L] feature
+ * panel, forward or backward.  With the flag and anything else -- fp32, D <= MGP_FUSED_MAX_D, S > 8 -- the code is
+ * exactly that of the plain call, with its bits and its refusals (forward: S > 8 is the panel route; backward: S > 8 is
+ * MGP_E_BADARG naming S, fp32 is MGP_E_DTYPE).  Without the flag nothing changes: mgp_rff_sample_vjp still refuses
+ * D > MGP_FUSED_MAX_D.  Empty inputs as on the plain calls (forward: N = 0 writes nothing, L = 0 writes zeros; backward:
+ * N = 0 writes zeros to dtheta and nothing to dX, L = 0 the reverse; both outputs NULL: MGP_E_BADARG).
+ *
+ * Tile scheme: a 16 x 16 tile of phases in revolutions, t = sum_d x_d theta_d / (2 pi), comes out of
+ * v_mfma_f64_16x16x4_f64.  Both point sets are packed per call in MFMA fragment order, zero padded to K = 4 KS columns,
+ * KS = ceil(D / 4), and to whole tiles of 16 points; K is walked in slices of 8 k-steps, k ascending, one accumulator
+ * per pair; the streamed side goes through LDS, every lane loads the owned side as its own operand; rff_math.h turns
+ * the phase into sin / cos as on every route.  The tile then goes back in as the B operand of the contraction.  A
+ * workgroup of four waves owns 64 points and streams the other side in tiles of 16:
+ *     forward   owned rows n, streamed bases l:  out^T[s, n] += Wc^T[s, l] cos[l, n] + Ws^T[s, l] sin[l, n], S padded to 16
+ *     dtheta    owned bases l, streamed rows n:  dtheta^T[d, l] += X^T[d, n] q[n, l]
+ *     dX        owned rows n, streamed bases l:  dX^T[d, n] += theta^T[d, l] q[l, n]
+ * with q = cos a - sin b, a = sum_s G_s W[s, L + l] and b = sum_s G_s W[s, l] two small matrix products over s; `scale`
+ * is applied once at the end.  dtheta and dX are one kernel with the roles swapped; asking for both runs it twice.  The
+ * output accumulator of a wave is ceil(D / 16) tiles of four doubles per lane (rounded up to one of 3, 4, 5, 6, 8, 10,
+ * 12, 16; a padded tile multiplies zeros); above D = 256 the output dimensions are taken in groups = ceil(D / 256) equal
+ * groups of at most 256 (1 group on the forward) and every group recomputes the phases.
+ * Slots past the end of either point set are exact zeros in every fragment, weight and coordinate and are never stored.
+ *
+ * Split rule: the streamed side is cut into `nsplit` runs of `tps` tiles (the last may be shorter),
+ *     wg      = ceil(owned / 64) * groups
+ *     stiles  = ceil(streamed / 16)
+ *     nsplit  = wg >= 2 CUs ? 1 : max(1, min(ceil(2 CUs / wg), ceil(stiles / 16), 256))
+ *     tps     = ceil(stiles / nsplit),  nsplit = ceil(stiles / tps),  len = 16 tps
+ * Every split writes a partial; a finish kernel adds the partials in split order and scales.  No float atomics: two
+ * calls give the same bits.  Everything is packed per call: nothing is kept on the handle between calls.
+ *
+ * Scratch: the arena "gen" alone, counted by mgp_workspace_bytes, with a(x) = x rounded up to a multiple of 256,
+ * To = ceil(owned / 16), Ts = ceil(streamed / 16), DT = 16 ceil(D / 16):
+ *     forward   a(512 KS To) + a(512 KS Ts) + a(4096 Ts)              + (nsplit > 1 ? a(64 nsplit N) : 0)
+ *     backward  a(512 KS To) + a(512 KS Ts) + a(2048 To) + a(2048 Ts) + (nsplit > 1 ? a(8 nsplit owned DT) : 0)
+ * bytes, for both outputs the larger of the two passes, reserved once.  MGP_E_NOMEM from a fixed pool that is too
+ * small, never an allocation.
+ *
+ * Error (u = 2^-53, K = 4 KS, P = max_nl sum_d |x_nd theta_ld|), per output element:
+ *     |out(s, n) - exact|     <= u (8 + (K + 2) P + 2 len + nsplit + 2) |scale| sum_l (|W[s, l]| + |W[s, L + l]|)
+ *     |dtheta[l, d] - exact|  <= u (8 + (K + 2) P + S + len + nsplit + 4)
+ *                                |scale| sum_n sum_s |G(s, n)| (|W[s, l]| + |W[s, L + l]|) |x_n[d]|
+ * and the same for dX with theta_l[d] in place of x_n[d] and the sum over l -- the sums of absolute terms of the bound
+ * above.  8 + (K + 2) P is the per-feature bound of rff_math.h with its fma-chain term replaced by the order-free bound
+ * of a K-term sum (the order in which the hardware adds the four products of a k-step is not documented): 1 u for
+ * theta / (2 pi), K u for the products and additions, 1 u of slack for second-order terms, all relative to sum_d |x_d
+ * theta_d|; 8 u for the argument scaling and the polynomials.  S (backward) is the order-free bound of the S-term sums
+ * a and b; `len` the longest accumulation chain of one split, one product and one addition per streamed point (two on
+ * the forward: the cos and the sin term), again order-free; `nsplit` the additions of the finish kernel; and 2
+ * (forward) or 4 (backward) for the final scaling, the two products and the subtraction of q, and slack.
+ * tests/test_gpu_rff_anyd.py holds every output to it. */
+enum { MGP_RFF_ANYD = 16 };
+
 #ifdef __cplusplus
 }
 #endif
