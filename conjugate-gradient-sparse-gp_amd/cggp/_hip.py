@@ -23,6 +23,7 @@ PRE_EYE, PRE_JACOBI, PRE_BLOCK, PRE_DENSE, PRE_CALLBACK, PRE_LOWRANK, PRE_LOWRAN
 OP_DENSE, OP_SGPR, OP_KMM_LAMBDA, OP_KXX_NOISE, OP_KMM_LAMBDA_WIDE = 0, 1, 2, 3, 4
 OP_SGPR_ANYD, OP_KMM_LAMBDA_ANYD, OP_KXX_NOISE_ANYD = 5, 6, 7  # include/mgp_sweep_anyd.h
 OP_KMM_LAMBDA_WIDE_ANYD = 8  # include/mgp_sweep_anyd.h: the many-column form above 32 dimensions
+OP_KXX_NOISE_SYM_ANYD = 9  # include/mgp.h: each unordered pair once on the matrix cores above 32 dimensions
 
 KERNEL_KINDS = {"se": SE, "matern12": MATERN12, "matern32": MATERN32, "matern52": MATERN52}
 

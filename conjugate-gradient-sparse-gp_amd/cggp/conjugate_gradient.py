@@ -237,6 +237,34 @@ def wide_anyd_auto(dtype, D, columns, M):
             and int(M) >= WIDE_ANYD_AUTO_MIN_M)
 
 
+# `sym_anyd="auto"` takes the symmetric form above 32 dimensions (`MGP_OP_KXX_NOISE_SYM_ANYD`, include/mgp.h) where it
+# took at most 0.9 of the time of the FASTER of the two existing routes (`MGP_OP_KXX_NOISE`'s panels,
+# `MGP_OP_KXX_NOISE_ANYD`) at every measured point of a region: fp64, SYM_ANYD_AUTO_MIN_D <= D <= SYM_ANYD_AUTO_MAX_D,
+# SYM_ANYD_AUTO_MIN_COLUMNS <= columns <= SYM_ANYD_AUTO_MAX_COLUMNS and N >= SYM_ANYD_AUTO_MIN_N
+# -- N in {2^14, 2^16, 2^17}, D in {33, 77, 90, 128, 512}, 1, 5, 8, 16 and 32 columns, SE and Matern-3/2
+# (profiles/kxx_sym_anyd_times.json).  Measured, new / faster existing route: 0.26 - 0.81 in the region
+# below (96 points); outside it 0.82 - 1.10 at one column and 1.18 - 1.21 at D = 512 with 32 columns (0.59 - 0.75 at
+# D = 512 with 5 to 16 columns: a valid region too, but the smaller one).  None for the column count would mean that no
+# region qualifies and "auto" is False.
+SYM_ANYD_AUTO_MIN_COLUMNS = 5
+SYM_ANYD_AUTO_MAX_COLUMNS = 32
+SYM_ANYD_AUTO_MIN_N = 1 << 14
+SYM_ANYD_AUTO_MIN_D = 33
+SYM_ANYD_AUTO_MAX_D = 128
+
+
+def check_sym_anyd(sym_anyd, name="sym_anyd"):
+    """`sym_anyd` as given, or `ValueError`: False, True or "auto"."""
+    return check_wide(sym_anyd, name)
+
+
+def sym_anyd_auto(dtype, D, columns, N):
+    """The rule behind `sym_anyd="auto"`."""
+    return (SYM_ANYD_AUTO_MIN_COLUMNS is not None and dtype == torch.float64
+            and SYM_ANYD_AUTO_MIN_D <= int(D) <= SYM_ANYD_AUTO_MAX_D
+            and SYM_ANYD_AUTO_MIN_COLUMNS <= int(columns) <= SYM_ANYD_AUTO_MAX_COLUMNS and int(N) >= SYM_ANYD_AUTO_MIN_N)
+
+
 def anyd_matvec(fused_anyd, which, spec, X, *args, **kwargs):
     """`ops.knm_matvec`, `ops.kmn_matvec` or `ops.kxx_matvec` (`which` = "knm", "kmn", "kxx"; the arguments after `spec`
     are theirs), or its `_anyd` form under the rule of `use_fused_anyd`: the one helper the models route their direct
@@ -316,10 +344,16 @@ class KxxNoiseOperator(LinearOperator):
     system of exact GP regression, `GPR`'s K + s2 I without the [N,N] matrix.  Single device.
 
     `fused_anyd` (False, True or "auto"): `MGP_OP_KXX_NOISE_ANYD` -- at D > 32 in fp64 the fused any-D sweep instead of
-    kernel panels; elsewhere the plain kind's bits."""
+    kernel panels; elsewhere the plain kind's bits.
 
-    def __init__(self, kernel, X, noise_variance, fused_anyd=False):
+    `sym_anyd` (False, True or "auto"): at D > 32 in fp64, `MGP_OP_KXX_NOISE_SYM_ANYD` -- each unordered pair of rows
+    once on the fp64 matrix cores, up to 16 right-hand sides per pass.  It is asked first: True, or "auto" and
+    `sym_anyd_auto(dtype, D, columns, N)`, takes the kind; otherwise, and at D <= 32 or in fp32 always, `fused_anyd`
+    decides as above."""
+
+    def __init__(self, kernel, X, noise_variance, fused_anyd=False, sym_anyd=False):
         self.fused_anyd = check_fused_anyd(fused_anyd)
+        self.sym_anyd = check_sym_anyd(sym_anyd)
         self.X = _hip.check_tensor(X, "X")
         if self.X.dim() != 2:
             raise ValueError(f"X must be [N, D], got {tuple(self.X.shape)}")
@@ -336,11 +370,19 @@ class KxxNoiseOperator(LinearOperator):
     def _struct(self):
         return self._struct_for(1)
 
+    def kind_for(self, columns):
+        """The operator kind libmgp is handed for `columns` right-hand sides."""
+        D, columns = self.X.shape[1], max(int(columns), 1)
+        if D > WIDE_MAX_D and self.dtype == torch.float64 and self.sym_anyd is not False:
+            if self.sym_anyd is True or sym_anyd_auto(self.dtype, D, columns, self.shape[0]):
+                return _hip.OP_KXX_NOISE_SYM_ANYD
+        anyd = use_fused_anyd(self.fused_anyd, self.dtype, D, columns)
+        return _hip.OP_KXX_NOISE_ANYD if anyd else _hip.OP_KXX_NOISE
+
     def _struct_for(self, columns):
         k = self.spec.struct(_hip.dtype_code(self.X))
         st = _hip.MgpOperator()
-        anyd = use_fused_anyd(self.fused_anyd, self.dtype, self.X.shape[1], max(int(columns), 1))
-        st.kind = _hip.OP_KXX_NOISE_ANYD if anyd else _hip.OP_KXX_NOISE
+        st.kind = self.kind_for(columns)
         st.dtype = k.dtype
         st.n = self.shape[0]
         st.kernel = ctypes.pointer(k)

@@ -16,7 +16,7 @@ import torch
 from . import ops
 from .conjugate_gradient import (ConjugateGradient, KmmLambdaOperator, KxxNoiseOperator, PivotedCholeskyPreconditioner,
                                  SgprNormalOperator, SubsampledNormalPreconditioner, anyd_matvec, check_fused_anyd,
-                                 check_fused_variance, check_wide, use_fused_variance)
+                                 check_fused_variance, check_sym_anyd, check_wide, use_fused_variance)
 from .kernels import InducingPoints, Kuf, Kuu, inducingpoint_wrapper  # noqa: F401 (InducingPoints re-exported)
 from .likelihoods import Gaussian
 from .slq import slq_log_quadratic
@@ -1070,14 +1070,17 @@ class GPR:
     the Cholesky path the option is ignored: the exact variance is cheaper there.
     `fused_anyd` (False, True or "auto") is handed to the `KxxNoiseOperator` and is the rule of the model's own
     k(X*, X) products: at D > 32 in fp64 libmgp's fused any-D sweeps (include/mgp_sweep_anyd.h), not kernel panels.
+    `sym_anyd` (False, True or "auto") is handed to the `KxxNoiseOperator` alone: at D > 32 in fp64 the CG path solves
+    on `MGP_OP_KXX_NOISE_SYM_ANYD`, each unordered pair of rows once on the fp64 matrix cores.
     `log_marginal_likelihood` needs log|K + s2 I| and exists on the Cholesky path only;
     `log_marginal_likelihood_estimate` is its matrix-free stochastic Lanczos estimate at any N.
     """
 
     def __init__(self, data, kernel, noise_variance=1.0, conjugate_gradient=None, *, solver="auto",
                  cholesky_max_n=16384, variance_chunk_bytes=256 << 20, variance="solve", variance_rank=128,
-                 fused_anyd=False):
+                 fused_anyd=False, sym_anyd=False):
         self.fused_anyd = check_fused_anyd(fused_anyd)
+        self.sym_anyd = check_sym_anyd(sym_anyd)
         if solver not in ("auto", "cholesky", "cg"):
             raise ValueError(f"unknown solver {solver!r}")
         if variance not in ("solve", "lanczos"):
@@ -1136,7 +1139,7 @@ class GPR:
         self._sync()
         if self._op is None:
             self._op = KxxNoiseOperator(self.kernel, self.data[0], self.likelihood.variance,
-                                        fused_anyd=self.fused_anyd)
+                                        fused_anyd=self.fused_anyd, sym_anyd=self.sym_anyd)
         return self._op
 
     def solve(self, rhs):

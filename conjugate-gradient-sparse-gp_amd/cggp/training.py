@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from . import _hip, ops
 from .conjugate_gradient import (ConjugateGradient, anyd_matvec, check_fused_anyd, check_fused_point_grads,
-                                 use_fused_point_grads)
+                                 check_sym_anyd, use_fused_point_grads)
 from .kernels import Stationary
 from .models import check_data_term, check_pathwise, draw_pathwise, eval_logdet, rademacher
 
@@ -813,13 +813,15 @@ class _GPRLmlEstimate(torch.autograd.Function):
     unbiased because E[z z^T] = P whatever P is."""
 
     @staticmethod
-    def forward(ctx, variance, lengthscales, s2, X, Y, probes, kind, cg, num_probes=None, seed=0, fused_anyd=False):
+    def forward(ctx, variance, lengthscales, s2, X, Y, probes, kind, cg, num_probes=None, seed=0, fused_anyd=False,
+                sym_anyd=False):
         from . import kernels
         from .models import GPR
         cls = {"se": kernels.SquaredExponential, "matern12": kernels.Matern12, "matern32": kernels.Matern32,
                "matern52": kernels.Matern52}[kind]
         kern = cls(variance=float(variance), lengthscales=[float(v) for v in lengthscales.reshape(-1)])
-        model = GPR((X, Y), kern, noise_variance=float(s2), conjugate_gradient=cg, solver="cg", fused_anyd=fused_anyd)
+        model = GPR((X, Y), kern, noise_variance=float(s2), conjugate_gradient=cg, solver="cg", fused_anyd=fused_anyd,
+                    sym_anyd=sym_anyd)
         if probes is None:
             est, alpha, W, Z = model._lml_estimate(num_probes=num_probes, seed=seed)
         else:
@@ -840,8 +842,8 @@ class _GPRLmlEstimate(torch.autograd.Function):
         n_l = int(np.prod(ctx.l_shape)) if len(ctx.l_shape) else 1
         gl = torch.tensor(dls if n_l > 1 else [sum(dls)], dtype=torch.float64).reshape(ctx.l_shape)
         grads = (g * torch.tensor(dvar, dtype=torch.float64), g * gl, g * torch.tensor(ds2, dtype=torch.float64),
-                 None, None, None, None, None, None, None, None)
-        return grads[:len(ctx.needs_input_grad)]  # `num_probes`, `seed` and `fused_anyd` are optional in apply()
+                 None, None, None, None, None, None, None, None, None)
+        return grads[:len(ctx.needs_input_grad)]  # `num_probes`, `seed`, `fused_anyd`, `sym_anyd` are optional in apply()
 
 
 class TrainableGPR:
@@ -862,11 +864,13 @@ class TrainableGPR:
     search may see the two disagree: Adam is the tested optimiser here.
 
     `fused_anyd` (False, True or "auto"): the setting of the matrix-free estimate's `KxxNoiseOperator` and of the
-    frozen model, as on `models.GPR`; the gradient call (`mgp_kxx_grad`) is not affected."""
+    frozen model, as on `models.GPR`; the gradient call (`mgp_kxx_grad`) is not affected.  `sym_anyd` (False, True or
+    "auto"): the same for `MGP_OP_KXX_NOISE_SYM_ANYD`, the symmetric operator above 32 dimensions."""
 
     def __init__(self, kernel, noise_variance, X, Y, *, num_probes=None, probe_seed=0, conjugate_gradient=None,
-                 fused_anyd=False):
+                 fused_anyd=False, sym_anyd=False):
         self.fused_anyd = check_fused_anyd(fused_anyd)  # the matrix-free estimate's operator and the frozen model's
+        self.sym_anyd = check_sym_anyd(sym_anyd)
         self.kernel = TrainableKernel(kernel)
         self.likelihood_variance = Parameter(noise_variance)
         self.X, self.Y = X, Y
@@ -911,7 +915,7 @@ class TrainableGPR:
                 ls = ls.reshape(1)
             return _GPRLmlEstimate.apply(self.kernel.variance_p(), ls, s2, X.contiguous(), Y.contiguous(), None,
                                          self.kernel.name, self.conjugate_gradient, self.num_probes, self.probe_seed,
-                                         self.fused_anyd)
+                                         self.fused_anyd, self.sym_anyd)
         if self.num_probes is not None:
             probes = self.probes if self.probes.shape[0] == N else None
             if probes is None:  # another row count than the model's own data: a draw of that size
@@ -922,7 +926,8 @@ class TrainableGPR:
             if ls.dim() == 0:
                 ls = ls.reshape(1)
             return _GPRLmlEstimate.apply(self.kernel.variance_p(), ls, s2, X.contiguous(), Y.contiguous(), probes,
-                                         self.kernel.name, self.conjugate_gradient, None, 0, self.fused_anyd)
+                                         self.kernel.name, self.conjugate_gradient, None, 0, self.fused_anyd,
+                                         self.sym_anyd)
         K = self.kernel.K(X) + s2.to(X.device) * torch.eye(N, dtype=X.dtype, device=X.device)
         L = torch.linalg.cholesky(K)
         v = torch.linalg.solve_triangular(L, Y, upper=False)
@@ -941,9 +946,9 @@ class TrainableGPR:
         if self.num_probes is not None:
             return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
                        conjugate_gradient=self.conjugate_gradient, solver="cg", fused_anyd=self.fused_anyd,
-                       **gpr_kwargs)
+                       sym_anyd=self.sym_anyd, **gpr_kwargs)
         return GPR((self.X, self.Y), self.kernel.frozen(), noise_variance=self.likelihood_variance.value,
-                   solver="cholesky", fused_anyd=self.fused_anyd, **gpr_kwargs)
+                   solver="cholesky", fused_anyd=self.fused_anyd, sym_anyd=self.sym_anyd, **gpr_kwargs)
 
 
 def sgpr_bound(Kmm_j, Q, b, yy, s2, variance, N):

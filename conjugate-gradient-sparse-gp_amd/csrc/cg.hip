@@ -436,6 +436,8 @@ int apply_operator(mgp_handle* h, const mgp_operator* op, const T* P, long Bt, T
       return mgp_kxx(h, op->kernel, op->X, n, op->s2, VecView{P, 1, n}, (int)Bt, VecViewMut{out, 1, n}, gate);
     case MGP_OP_KXX_NOISE_ANYD:
       return mgp_kxx_anyd(h, op->kernel, op->X, n, op->s2, VecView{P, 1, n}, (int)Bt, VecViewMut{out, 1, n}, gate);
+    case MGP_OP_KXX_NOISE_SYM_ANYD:  // each unordered pair once on the matrix cores (kxx_sym_anyd.hip); else MGP_OP_KXX_NOISE
+      return mgp_kxx_sym_anyd(h, op->kernel, op->X, n, op->s2, P, Bt, out, gate);
     case MGP_OP_SGPR_ANYD:  // the two local sweeps by the fused any-D kernel where it serves; everything else as below
     case MGP_OP_SGPR: {
       const auto sweep = op->kind == MGP_OP_SGPR_ANYD ? mgp_sweep_anyd : mgp_sweep;
@@ -555,7 +557,8 @@ int check_operator(mgp_handle* h, const mgp_operator* op) {
       return mgp_fail(h, MGP_E_BADARG, "give either the allreduce hook or a communicator, not both");
     if (sgpr && op->allreduce && op->world_size < 1)
       return mgp_fail(h, MGP_E_BADARG, "allreduce hook needs world_size >= 1");
-  } else if (op->kind == MGP_OP_KXX_NOISE || op->kind == MGP_OP_KXX_NOISE_ANYD) {
+  } else if (op->kind == MGP_OP_KXX_NOISE || op->kind == MGP_OP_KXX_NOISE_ANYD ||
+             op->kind == MGP_OP_KXX_NOISE_SYM_ANYD) {
     MGP_TRY(mgp_check_kernel(h, op->kernel));
     if (op->kernel->dtype != op->dtype) return mgp_fail(h, MGP_E_DTYPE, "operator/kernel dtype mismatch");
     if (op->N != op->n || !op->X) return mgp_fail(h, MGP_E_SHAPE, "K_XX operator needs X with N == n");
@@ -904,6 +907,12 @@ int pcg_solve_t(mgp_handle* h, const mgp_operator* op, const mgp_precond* pre, c
              mgp_kmm_wide_serves(op->kernel)) {
     MGP_TRY(mgp_kmm_wide_prepare(h, op->kernel, op->Z, op->M, Bt, nullptr));
     wide_hold.hold(op->Z, op->M);
+  }
+  // the symmetric operator above 32 dimensions: the same for X and the kxx arena
+  SymHold sym_hold(h);
+  if (op->kind == MGP_OP_KXX_NOISE_SYM_ANYD && mgp_kxx_sym_anyd_serves(op->kernel)) {
+    MGP_TRY(mgp_kxx_sym_anyd_prepare(h, op->kernel, op->X, op->N, Bt, nullptr));
+    sym_hold.hold(op->X, op->N);
   }
   MGP_TRY(cg.start(V0, persist));
   MGP_TRY(persist ? cg.run_persist() : (dense1 && h->poll_pipeline) ? cg.run_dense1_pipelined() : cg.run_polled());

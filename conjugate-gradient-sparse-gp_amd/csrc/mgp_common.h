@@ -36,6 +36,10 @@ struct mgp_handle {
   int kxx_mode = 0;  // mgp_kxx_matvec / MGP_OP_KXX_NOISE: 0 = symmetric kernel where it serves (fp64, D <= 32, N >=
                      // kxx_min_n), 1 = wherever it can (MGP_KXX=sym), 2 = the plain sweep mgp_sweep(X, X) + s2 V (MGP_KXX=plain)
   long kxx_min_n = 1L << 16;  // MGP_KXX_MIN_N
+  // symmetric operator above 32 dimensions (MGP_OP_KXX_NOISE_SYM_ANYD, kxx_sym_anyd.hip): the X whose pack stands at the
+  // front of kxx for the solve under way (SymHold); null outside a solve, where every application packs for itself
+  const void* sym_pack_src = nullptr;
+  long sym_pack_n = 0;
   // hyper-parameter bilinear forms of k(X,X) (kxx_grad.hip): packed rows, packed columns, workgroup partials -- or,
   // on the panel route, one row panel of G = U V^T
   void* kgrad = nullptr;
@@ -180,7 +184,22 @@ struct WideHold {
   ~WideHold() { release(); }
 };
 
-constexpr int MGP_PROF_CLK_WORDS = 64;        // per profiled launch: 16 slots x (real0, clk0, real1, clk1)
+// the same guard for MGP_OP_KXX_NOISE_SYM_ANYD: X is packed once at the front of the kxx arena and held until the solve ends
+struct SymHold {
+  mgp_handle* h;
+  explicit SymHold(mgp_handle* hh) : h(hh) { release(); }
+  void hold(const void* X, long N) {
+    h->sym_pack_src = X;
+    h->sym_pack_n = N;
+  }
+  void release() {
+    h->sym_pack_src = nullptr;
+    h->sym_pack_n = 0;
+  }
+  ~SymHold() { release(); }
+};
+
+constexpr int MGP_PROF_CLK_WORDS = 64;       // per profiled launch: 16 slots x (real0, clk0, real1, clk1)
 constexpr int MGP_PROF_CLK_LAUNCHES = 8192;  // launches with stamps between two mgp_profile_enable(1) calls
 
 // the stamp slot block of the NEXT profiled launch (nullptr when profiling is off or the block is used up)
@@ -438,6 +457,14 @@ bool mgp_kmm_wide_anyd_serves(const mgp_kernel* k);
 int mgp_kmm_wide_anyd_prepare(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, int64_t Bt, const int* gate);
 int mgp_kmm_wide_anyd_apply(mgp_handle* h, const mgp_kernel* k, const void* Z, int64_t M, const void* lambda,
                             const void* P, int64_t Bt, void* out, const int* gate);
+// kxx_sym_anyd.hip (MGP_OP_KXX_NOISE_SYM_ANYD, include/mgp.h): out[Bt, N] = P[Bt, N] (k(X, X) + s2 I), each unordered
+// pair once on the matrix cores, at fp64 and D > MGP_FUSED_MAX_D (mgp_kxx_sym_anyd_serves); elsewhere mgp_kxx itself.
+// prepare reserves the kxx arena for Bt right-hand sides and packs X at its front; the product packs for itself unless
+// a SymHold names this X.  gate: device int, every kernel of the route skips if 0
+bool mgp_kxx_sym_anyd_serves(const mgp_kernel* k);
+int mgp_kxx_sym_anyd_prepare(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, int64_t Bt, const int* gate);
+int mgp_kxx_sym_anyd(mgp_handle* h, const mgp_kernel* k, const void* X, int64_t N, double s2, const void* P,
+                     int64_t Bt, void* out, const int* gate);
 // rff_anyd.hip (MGP_RFF_ANYD, include/mgp_pathwise.h): the fused prior sample and its backward pass at fp64,
 // MGP_FUSED_MAX_D < D <= MGP_MAX_D and 1 <= S <= 8 (mgp_rff_anyd_serves), on arguments rff.hip / rff_grad.hip have checked
 bool mgp_rff_anyd_serves(int dtype, int D, int S);

@@ -91,8 +91,39 @@ enum { MGP_PRE_EYE = 0, MGP_PRE_JACOBI = 1, MGP_PRE_BLOCK = 2, MGP_PRE_DENSE = 3
  * that is too small): 8 M (D' + 1) rounded up to 256, plus 8 t r' (min(M', 2^16) / t + s) rounded up to 256 bytes for
  * the widest group, r = min(Bt, 256) columns (and Bt mod 256 when Bt > 256), r' = r rounded up to 16, t = 128 for
  * r <= 128 and 64 above, M' = M rounded up to t, D' = D rounded up to 2, 4, 8, 16 or 32, s <= 4 CUs + 1 the workgroups
- * added by the split -- at most 8 M (D' + 1) + 512 r' (1024 + 4 CUs + 1) + 512 bytes. */
-enum { MGP_OP_DENSE = 0, MGP_OP_SGPR = 1, MGP_OP_KMM_LAMBDA = 2, MGP_OP_KXX_NOISE = 3, MGP_OP_KMM_LAMBDA_WIDE = 4 };
+ * added by the split -- at most 8 M (D' + 1) + 512 r' (1024 + 4 CUs + 1) + 512 bytes.
+ * MGP_OP_KXX_NOISE_SYM_ANYD: MGP_OP_KXX_NOISE above MGP_FUSED_MAX_D dimensions on the fp64 matrix cores -- the same
+ * fields (kernel, X, N == n, s2), the same checks, the same meaning out[Bt, N] = P[Bt, N] (k(X, X) + s2 I), for fp64 and
+ * MGP_FUSED_MAX_D < D <= MGP_MAX_D with no kernel panel in memory (csrc/kxx_sym_anyd.hip).  Rows go in blocks of
+ * TB = 128 points; every unordered pair of blocks {I, (I + d) mod nb}, d = 0 .. nb/2, is evaluated once (the diagonal
+ * block whole, feeding only its own rows) and each profiled 16 x 16 tile is contracted twice, with the right-hand sides
+ * of both blocks, for up to 16 right-hand sides at once; more go in groups of 16 plus a remainder.  The distance is
+ * the expansion form of mgp_sweep_anyd.h (K = D + 2 on v_mfma_f64_16x16x4_f64 in slices of 32 columns, k ascending, the
+ * profile once after the last slice).  Partial sums go to slots with one writer per slot and row, added in slot order
+ * by a second kernel that scales by the variance and adds s2 P: no float atomics, two calls are bit-identical.
+ * mgp_pcg_solve / mgp_pcg_solve_record pack X once, before the loop, and hold the pack to the end of the solve;
+ * mgp_operator_apply packs per call, so X may change in place between calls.  Every launch reads the gate word;
+ * N = 0 or Bt = 0 writes nothing.  Fallbacks: fp32 or D <= MGP_FUSED_MAX_D take exactly the code of MGP_OP_KXX_NOISE
+ * and give its bits.
+ * Scratch, the arena of mgp_kxx_matvec alone ("kxx"; counted by mgp_workspace_bytes; MGP_E_NOMEM from a fixed pool that
+ * is too small, nothing is allocated then):
+ *     bytes = align256(8 * 64 * KS * N' / 16) + 2 * align256(8 * 16 * N') + align256(8 * (S + ceil(S / DC)) * N' * r)
+ * with N' = N rounded up to 128, KS = ceil((D + 2) / 4), r = min(Bt, 16) (with Bt > 16 and Bt mod 16 > 0 the last
+ * term is the larger of the terms of r = 16 and r = Bt mod 16), nb = N' / 128, nd = nb/2 + 1,
+ * DC = min(ceil(nd / min(max(ceil(2 CUs / nb), 1), nd)), maxs - 1) the values of d one workgroup chains,
+ * maxs = min(max(2, 2^29 / (8 N' r)), 32768) and S = min(nd, max(1, maxs / (DC + 1)) DC) the values of d per launch:
+ * the slots of a launch stay inside 2^29 bytes (two slots where one exceeds 2^28), as those of mgp_kxx_matvec.
+ * Error, for every element, u = 2^-53:
+ *     |out[b, i] - exact| <= sum_j |P[b, j]| pairbound(i, j) + u (terms + slots + 3) sum_j |P[b, j] K[i, j]|
+ *                            + 2 u |s2 P[b, i]|
+ * pairbound(i, j) the bound of the expansion-form distance through the profile (tests/pair_reference.py's pair_bound,
+ * as for MGP_OP_KMM_LAMBDA_WIDE_ANYD); terms = 128 DC, the longest chain of products one accumulator takes on the
+ * matrix cores (the DC blocks a workgroup streams past the block it keeps, padding included; the chain of the streamed
+ * side -- 32 products per wave and 3 sums of waves -- is shorter); slots = nd + ceil(nd / DC) + 2 ceil(nd / S), the
+ * sums of the finish kernel over every launch (a slot per d, one per chunk, the running sum); 3 = the product with the variance, the product s2 P[b, i] and the last sum.
+ * The distance cancels where a direct difference does not: this error is why the kind is opt-in. */
+enum { MGP_OP_DENSE = 0, MGP_OP_SGPR = 1, MGP_OP_KMM_LAMBDA = 2, MGP_OP_KXX_NOISE = 3, MGP_OP_KMM_LAMBDA_WIDE = 4,
+       MGP_OP_KXX_NOISE_SYM_ANYD = 9 };
 
 typedef struct mgp_handle mgp_handle;
 /* one RCCL communicator rank (wraps ncclComm_t); see "collectives" below */
